@@ -8,6 +8,15 @@ encode of one 1024:1024 x 1 KiB stripe whose shards already sit in HBM
 (loss pattern of the reference's benches/benchmarks.rs:113-138) is timed the
 same way and reported beside the headline value.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps of the primary workload and prints the line with `value` and
+`ms_per_step`; nothing else.  --full adds everything described below (decode,
+batched, host and object-API legs, roofline, device copy, the other configs,
+the sharded sub-object, the CPU baseline), each still under its --no-* switch.
+--dump-outputs DIR writes the recovery shards the last timed step produced to
+DIR/recovery.npy (float32; inputs come from a fixed seed, so two builds can be
+compared element for element).
+
 --gpus N > 1: the parent process (which never touches the GPU) starts N ranks
 with torch.distributed.run, one process per GPU (RCCL = the "nccl" backend).
 Every N reports the SAME primary workload: the headline stripe on every rank
@@ -77,6 +86,13 @@ def parse():
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--config", default=None, choices=sorted(CONFIGS),
                    help=f"default: {HEADLINE} (independent stripes per rank) at every N")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline steps: decode, batched, host, object-API, roofline, device-copy, "
+                        "configs[2..4] and the CPU baseline (each still subject to its --no-* switch); "
+                        "without it only the primary workload's steps are timed")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed (the recovery shards) to "
+                        "DIR/<name>.npy as float32 (a fixed seeded sample if larger than 64 MB)")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-copy", action="store_true", help="skip the 1 GiB device-copy context measurement")
@@ -94,7 +110,10 @@ def parse():
     p.add_argument("--shape-table", action="store_true",
                    help="time the reference README's shape table (README.md:27-45, 1 KiB shards): device "
                         "encode and 1 %% / 100 %% decode, the route each takes, and the AVX2 port on one core")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -244,6 +263,28 @@ def make_timer(world, dev):
     return timed, gpu_time
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname, world, rank, **arrays):
+    """--dump-outputs: every device array of the timed path's last step as DIR/<name>.npy
+    (float32, row-major; at world > 1 <name>_rank<r>.npy).  An array whose float32 form would
+    pass its share of 64 MB is sampled at flat indices drawn once from a fixed seed, in
+    ascending order, so that two builds write the same elements."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    cap = DUMP_MAX_BYTES // (4 * len(arrays) * world)
+    for name, t in arrays.items():
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(20240).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out = t.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), out)
+
+
 def load_pmc(kernel, config):
     """Per-launch PMC figures of `kernel` in the bench of `config` from the newest committed
     summary that has them (profiles/<tag>/traffic.json, written by tools/pmc_traffic.py from
@@ -379,14 +420,23 @@ def config_block(args, rs, ctx, name, world, dev, encode=True, decode=True):
 # ---------------------------------------------------------------------------
 # one stripe per step (configs[1..3]); N > 1: independent stripes per rank
 
+def stripe_inputs(config, rank, dev):
+    """The original shards of `config` on rank `rank` (fixed seed: the same bytes in every run)
+    and the generator, for the legs that draw more."""
+    import torch
+
+    N, _, S = CONFIGS[config]
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234 + rank)
+    return torch.randint(0, 256, (N, S), dtype=torch.uint8, device=dev, generator=g), g
+
+
 def stripe_bench(args, rs, ctx, config, world, rank, dev):
     import torch
 
     N, M, S = CONFIGS[config]
     timed, gpu_time = make_timer(world, dev)
-    g = torch.Generator(device=dev)
-    g.manual_seed(1234 + rank)
-    d_orig = torch.randint(0, 256, (N, S), dtype=torch.uint8, device=dev, generator=g)
+    d_orig, g = stripe_inputs(config, rank, dev)
     d_rec = torch.empty((M, S), dtype=torch.uint8, device=dev)
     d_out = torch.empty((N, S), dtype=torch.uint8, device=dev)
     stream = torch.cuda.Stream(device=dev)
@@ -397,9 +447,16 @@ def stripe_bench(args, rs, ctx, config, world, rank, dev):
 
     # ---- headline: encode -------------------------------------------------
     wall = timed(enc, args.steps, args.warmup)
-    gpu_t = gpu_time(enc, args.steps, stream)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, world, rank, recovery=d_rec)
     step_bytes = (N + M) * S
     value = step_bytes * args.steps * world / wall / 2**30
+    if not args.full:
+        # the plain run: the headline steps and nothing else
+        if rank == 0:
+            print(json.dumps(headline_line(args, rs, config, world, wall, value)))
+        return
+    gpu_t = gpu_time(enc, args.steps, stream)
     roofline = roofline_of(rs, ctx, enc, args.profile_steps, step_bytes, config, gpu_t / args.steps)
 
     # ---- decode at 1 % and 100 % loss (benchmarks.rs:113-138) --------------
@@ -515,15 +572,8 @@ def stripe_bench(args, rs, ctx, config, world, rank, dev):
         cpu = cpu_baseline(args.cpu_seconds, N, M, S)
 
     if rank == 0:
-        line = {
-            "metric": METRIC, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(wall / args.steps * 1e3, 6),
-            "us_per_step": round(wall / args.steps * 1e6, 2), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic (uniform random bytes)",
-            "config": {"workload": f"encode {N}:{M} x {S} B, device-resident (rs_encode_device)",
-                       "original_count": N, "recovery_count": M, "shard_bytes": S,
-                       "rate": "high" if rs.use_high_rate(N, M) == 1 else "low",
-                       "parallelism": f"replicas x{world} (independent stripes)"},
+        line = headline_line(args, rs, config, world, wall, value)
+        line.update({
             "gpu_event_ms_per_step": round(gpu_t / args.steps * 1e3, 5),
             "decode_GiBps": decode,
             "batched": batched,
@@ -536,8 +586,24 @@ def stripe_bench(args, rs, ctx, config, world, rank, dev):
             "sharded": sharded,
             "config3": cfg3,
             "config4": cfg4,
-        }
+        })
         print(json.dumps(line))
+
+
+def headline_line(args, rs, config, world, wall, value):
+    """The result line of the primary workload's timed steps (all of a plain run's line)."""
+    N, M, S = CONFIGS[config]
+    return {
+        "metric": METRIC, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(wall / args.steps * 1e3, 6),
+        "us_per_step": round(wall / args.steps * 1e6, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic (uniform random bytes)",
+        "config": {"workload": f"encode {N}:{M} x {S} B, device-resident (rs_encode_device)",
+                   "original_count": N, "recovery_count": M, "shard_bytes": S,
+                   "rate": "high" if rs.use_high_rate(N, M) == 1 else "low",
+                   "parallelism": f"replicas x{world} (independent stripes)"},
+        "full": args.full,
+    }
 
 
 def object_api_bench(N, M, S, iters, warmup):
@@ -698,15 +764,18 @@ def sharded_bench(args, rs, ctx, world, rank, dev):
             compute()
 
     t_step = timed(step, args.steps, args.warmup) / args.steps
-    t_comp = timed(compute, args.steps, args.warmup) / args.steps
-    per_gpu = (N + M) * w
-    roofline = roofline_of(rs, ctx, compute, max(3, args.profile_steps // 10), per_gpu, SHARDED)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, world, rank, recovery=d_rec)
     total = (N + M) * S
-    cpu = None
-    if rank == 0 and not args.no_cpu:
-        cpu = cpu_baseline(min(args.cpu_seconds, 10.0), N, M, S)
+    t_comp = roofline = cpu = None
+    if args.full:
+        t_comp = timed(compute, args.steps, args.warmup) / args.steps
+        per_gpu = (N + M) * w
+        roofline = roofline_of(rs, ctx, compute, max(3, args.profile_steps // 10), per_gpu, SHARDED)
+        if rank == 0 and not args.no_cpu:
+            cpu = cpu_baseline(min(args.cpu_seconds, 10.0), N, M, S)
     if rank == 0:
-        print(json.dumps({
+        line = {
             "metric": "GiB/s (original+recovery) encode, device-resident, 32768:32768x65536B column-partitioned "
                       "+ RCCL all-gather",
             "value": round(total / t_step / 2**30, 3), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
@@ -715,12 +784,17 @@ def sharded_bench(args, rs, ctx, world, rank, dev):
             "config": {"workload": "encode 32768:32768 x 64 KiB (configs[4]), column slice of 64 KiB / n per GPU",
                        "original_count": N, "recovery_count": M, "shard_bytes": S, "slice_bytes": w,
                        "parallelism": f"column partition x{world} + all_gather_into_tensor (RCCL)"},
-            "encode_only": {"ms_per_step": round(t_comp * 1e3, 4), "GiBps": round(total / t_comp / 2**30, 3)},
-            "allgather_and_interleave_ms": round((t_step - t_comp) * 1e3, 4),
             "pipeline_pieces": shard.chunks if world > 1 else 1,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }))
+            "full": args.full,
+        }
+        if args.full:
+            line.update({
+                "encode_only": {"ms_per_step": round(t_comp * 1e3, 4), "GiBps": round(total / t_comp / 2**30, 3)},
+                "allgather_and_interleave_ms": round((t_step - t_comp) * 1e3, 4),
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+            })
+        print(json.dumps(line))
 
 
 # ---------------------------------------------------------------------------

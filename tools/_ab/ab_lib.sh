@@ -6,7 +6,7 @@ LIB=reed-solomon-simd_amd/lib/librs_mi355x.so
 for ((i = 0; i < R; ++i)); do
   for v in A B; do
     cp tools/_ab/lib$v.so $LIB
-    line=$(timeout -k 10 300 python -u bench.py "$@" 2>/dev/null | tail -1) || { echo "$v failed"; exit 1; }
+    line=$(timeout -k 10 300 python -u bench.py --full "$@" 2>/dev/null | tail -1) || { echo "$v failed"; exit 1; }
     echo "$v $(echo "$line" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())

@@ -5,7 +5,7 @@ set -euo pipefail
 source "$(dirname "$0")/ab_common.sh"
 TAG=$1; R=$2; shift 2
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-ARGS="--no-cpu --no-host --no-copy --batch 1 --steps 200 --warmup 20"
+ARGS="--full --no-cpu --no-host --no-copy --batch 1 --steps 200 --warmup 20"
 for r in $(seq 1 $R); do
   for v in "$@"; do
     use_lib $v

@@ -20,7 +20,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -3 "$OUT/pytest_gpu.log"
 fi
 
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 cat "$OUT/bench.json"
 
 # profile one bench command: kernel trace + 3 PMC passes (separate runs)
@@ -29,25 +29,25 @@ profile() {  # profile <config-name> <bench args...>
   shift
   local d="$OUT/pmc/$cfg"
   mkdir -p "$d" "$OUT/kt"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/kt/$cfg" -o run -- python3 bench.py "$@" \
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/kt/$cfg" -o run -- python3 bench.py --full "$@" \
     > "$OUT/kt_$cfg.log" 2>&1
-  timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE -f csv -d "$d/fetch" -o run -- python3 bench.py "$@" \
+  timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE -f csv -d "$d/fetch" -o run -- python3 bench.py --full "$@" \
     > "$d/fetch.log" 2>&1
-  timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE -f csv -d "$d/write" -o run -- python3 bench.py "$@" \
+  timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE -f csv -d "$d/write" -o run -- python3 bench.py --full "$@" \
     > "$d/write.log" 2>&1
   timeout -s KILL 180 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES \
-    SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAVE_CYCLES -f csv -d "$d/sq" -o run -- python3 bench.py "$@" \
+    SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAVE_CYCLES -f csv -d "$d/sq" -o run -- python3 bench.py --full "$@" \
     > "$d/sq.log" 2>&1
   echo "profiled $cfg"
 }
 
 profile 1024x1024x1k --no-cpu --no-host --no-copy --no-sharded --no-configs --batch 1 --steps 200 --warmup 20
 if [ "${CONFIGS:-0}" = "1" ]; then  # the other single-GPU BASELINE configs
-  timeout -k 10 300 python -u bench.py --no-cpu --config 32768x32768x1k --steps 50 --warmup 5 \
+  timeout -k 10 300 python -u bench.py --full --no-cpu --config 32768x32768x1k --steps 50 --warmup 5 \
     > "$OUT/bench_config3.json" 2>> "$OUT/bench.err"
-  timeout -k 10 300 python -u bench.py --no-cpu --config 8192x8192x64k --steps 10 --warmup 2 \
+  timeout -k 10 300 python -u bench.py --full --no-cpu --config 8192x8192x64k --steps 10 --warmup 2 \
     > "$OUT/bench_config4.json" 2>> "$OUT/bench.err"
-  timeout -k 10 300 python -u bench.py --config 32768x32768x64k --steps 10 --warmup 2 --cpu-seconds 5 \
+  timeout -k 10 300 python -u bench.py --full --config 32768x32768x64k --steps 10 --warmup 2 --cpu-seconds 5 \
     > "$OUT/bench_config5_n1.json" 2>> "$OUT/bench.err"
   profile 32768x32768x1k --no-cpu --no-host --no-copy --batch 1 --config 32768x32768x1k --steps 20 --warmup 3
   profile 8192x8192x64k --no-cpu --no-host --no-copy --batch 1 --config 8192x8192x64k --steps 5 --warmup 2
