@@ -30,7 +30,8 @@
  * Device-resident batch entry points (the performance path; no reference
  * counterpart because the reference engine only sees host slices):
  *   rs_encode_device / rs_decode_device (+ _strided, + _batch: many
- *   stripes of one shape in one launch)
+ *   stripes of one shape in one launch; rs_decode_device_batch_masks: the
+ *   batch decode with an erasure pattern per stripe)
  *
  * Thread-safety: a context may be shared by threads (like DefaultEngine:
  * Send + Sync, src/lib.rs:385-409): calls on one context are serialized on the
@@ -238,6 +239,44 @@ rs_status rs_decode_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  uint64_t recovery_stripe_stride, const uint8_t *recovery_present, void *d_restored,
                                  uint64_t restored_stride, uint64_t restored_stripe_stride, void *stream,
                                  rs_error *err);
+/* The batch decode with one erasure pattern PER STRIPE (a receiver doing FEC
+ * loses different packets in every block; a repair finds different shards
+ * missing in every object).  Matrices, strides and alignment rules are those of
+ * rs_decode_device_batch; original_present / recovery_present are HOST arrays of
+ * stripes x original_count / stripes x recovery_count bytes of 0/1, stripe-major
+ * (row b = stripe b's pattern).
+ *   Result: stripe b ends up exactly as if rs_decode_device_strided had been
+ * called on it with row b of the two masks: only its missing originals are
+ * written, absent input rows are never read, and a stripe with no missing
+ * original does no work and writes nothing.
+ *   Errors: argument checks first, in rs_decode_device_batch's order (null
+ * context / pointers -> RS_ERR_INVALID_ARGUMENT, then rs_validate, then the
+ * strides); stripes == 0 -> RS_OK.  Then every stripe's pattern is checked on
+ * the host, in stripe order, before any device work; a stripe with fewer than
+ * original_count shards in total cannot be decoded (NotEnoughShards).
+ *   stripe_status == NULL: all or nothing.  The first such stripe's error is
+ *     returned, with that stripe's original_received_count /
+ *     recovery_received_count and the stripe's number in err->index (an
+ *     extension: the reference's NotEnoughShards has no index); nothing is
+ *     launched and nothing is written.
+ *   stripe_status != NULL (HOST, stripes bytes): filled with one rs_status per
+ *     stripe (RS_OK also for stripes with nothing missing).  Stripes that cannot
+ *     be decoded are skipped -- their matrices are neither read nor written --
+ *     the others are decoded, and the call returns RS_OK.
+ *   Where rs_decode_device_batch runs a batch as one launch (decodes of up to
+ * 2^11 work rows on the column kernel) so does this call: the patterns travel
+ * to the device as per-stripe descriptors, copied on `stream` ahead of the
+ * launch (DESIGN.md "Batches of stripes").  Elsewhere the stripes decode one
+ * after another, each with its pattern.  Asynchronous on `stream`; scratch per
+ * (context, stream) like every device entry point. */
+rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                       uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                       const void *d_original, uint64_t original_stride,
+                                       uint64_t original_stripe_stride, const uint8_t *original_present,
+                                       const void *d_recovery, uint64_t recovery_stride,
+                                       uint64_t recovery_stripe_stride, const uint8_t *recovery_present,
+                                       void *d_restored, uint64_t restored_stride, uint64_t restored_stripe_stride,
+                                       uint8_t *stripe_status, void *stream, rs_error *err);
 
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x

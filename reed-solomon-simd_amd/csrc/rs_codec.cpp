@@ -1177,16 +1177,12 @@ void fft_pass_pruned(rs::PassArgs P, const Levels &lv, uint32_t k, uint32_t nd, 
                 true);
 }
 
-// Decode (rate_high.rs:172-254 / rate_low.rs:172-254).  Only missing original
-// rows of `restored` are written.
-//
-// Multi-level formal derivative (DESIGN.md "Formal derivative across passes"):
-// with X_k the IFFT output after levels 0..k and P_(k) the derivative terms of
-// level k's bits,  U = F_top(P_(top) X_top),  V_{m-2} = F_{m-2}((I + P_(m-2)) X_{m-2} + U),
-// V_k = F_k(P_(k) X_k + V_{k+1}) for k < m-2, and V_0 is FFT(derivative(IFFT)).
-void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64_t N, uint64_t M,
-                const uint8_t *orig, const uint8_t *orig_present, const uint8_t *rec, const uint8_t *rec_present,
-                uint8_t *restored, hipStream_t s) {
+// Work rows of a decode: the second shard kind starts at row `chunk`, the last
+// shard sits at row end - 1, the transform has nd = 2^u rows.
+struct DecodeRows {
+    uint32_t chunk, end, nd, u;
+};
+DecodeRows decode_rows(rs_context *ctx, bool high, const Geom &g, uint64_t N, uint64_t M) {
     const uint32_t chunk = uint32_t(high ? next_pow2(M) : next_pow2(N));
     const uint32_t end = uint32_t(chunk + (high ? N : M));
     uint32_t nd = uint32_t(next_pow2(end)), u = ilog2(nd);
@@ -1200,6 +1196,21 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         nd = 1u << kMonoMinL;
         u = kMonoMinL;
     }
+    return {chunk, end, nd, u};
+}
+
+// Decode (rate_high.rs:172-254 / rate_low.rs:172-254).  Only missing original
+// rows of `restored` are written.
+//
+// Multi-level formal derivative (DESIGN.md "Formal derivative across passes"):
+// with X_k the IFFT output after levels 0..k and P_(k) the derivative terms of
+// level k's bits,  U = F_top(P_(top) X_top),  V_{m-2} = F_{m-2}((I + P_(m-2)) X_{m-2} + U),
+// V_k = F_k(P_(k) X_k + V_{k+1}) for k < m-2, and V_0 is FFT(derivative(IFFT)).
+void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64_t N, uint64_t M,
+                const uint8_t *orig, const uint8_t *orig_present, const uint8_t *rec, const uint8_t *rec_present,
+                uint8_t *restored, hipStream_t s) {
+    const DecodeRows dr = decode_rows(ctx, high, g, N, M);
+    const uint32_t chunk = dr.chunk, end = dr.end, nd = dr.nd, u = dr.u;
     // erasure vector + received flags per work row
     std::vector<uint8_t> &st = ws.h_state;
     st.assign(nd, 0);
@@ -1459,6 +1470,103 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         }
         fft_pass_pruned(P, lv, uint32_t(k), nd, st, out_map, s);
     }
+}
+
+// Presence bytes p[0 .. n) (non-zero = present) as bits [bit0, bit0 + n) of the
+// words w (clear there on entry; little-endian host); returns how many are set.
+// Eight bytes at a time where bit0 is byte aligned: the high bit of every
+// non-zero byte, gathered into one byte by a carry-free multiply.
+uint32_t put_present(const uint8_t *p, uint32_t n, uint32_t bit0, uint32_t *w) {
+    uint32_t have = 0, i = 0;
+    if (bit0 % 8 == 0) {
+        uint8_t *wb = reinterpret_cast<uint8_t *>(w) + bit0 / 8;
+        constexpr uint64_t k7f = 0x7F7F7F7F7F7F7F7Full;
+        for (; i + 8 <= n; i += 8) {
+            uint64_t x;
+            std::memcpy(&x, p + i, 8);
+            const uint64_t nz = ((((x & k7f) + k7f) | x) & ~k7f) >> 7;  // byte k = (p[i + k] != 0)
+            const uint8_t bits = uint8_t((nz * 0x0102040810204080ull) >> 56);  // bit k = byte k
+            wb[i / 8] = bits;
+            have += uint32_t(__builtin_popcount(bits));
+        }
+    }
+    for (; i < n; ++i)
+        if (p[i]) w[(bit0 + i) >> 5] |= 1u << ((bit0 + i) & 31), ++have;
+    return have;
+}
+
+// Decode of a batch of stripes with one erasure pattern per stripe
+// (rs_decode_device_batch_masks): orig_present / rec_present hold g.stripes rows
+// of N / M bytes, skip[b] != 0 leaves stripe b alone (nothing missing, or not
+// decodable).  Where decode_dev takes a batch as one launch (the fused route)
+// this is one launch of k_mono_masks: the patterns travel as per-stripe
+// descriptors (rs_device.hpp MonoMaskArgs) built in the workspace's pinned
+// staging and copied on `s` ahead of the launch; the plain plan with the whole
+// destination map (the narrowed map and the split plan are decisions about ONE
+// pattern; the reveal writes erased rows only either way).  Elsewhere the
+// stripes decode one after another, as decode_dev's batches do.
+void decode_masks_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64_t N, uint64_t M,
+                      const uint8_t *orig, const uint8_t *orig_present, const uint8_t *rec,
+                      const uint8_t *rec_present, uint8_t *restored, const uint8_t *skip, hipStream_t s) {
+    const DecodeRows dr = decode_rows(ctx, high, g, N, M);
+    const uint32_t chunk = dr.chunk, end = dr.end, nd = dr.nd, u = dr.u;
+    if (!(use_mono(ctx, u, g, 1) && rs::mono_staged(int(u), 1) && nd <= rs::kMonoFusedRows)) {
+        Geom g1 = g;
+        g1.stripes = 1;
+        for (uint32_t b = 0; b < g.stripes; ++b)
+            if (!skip[b])
+                decode_dev(ctx, ws, high, g1, N, M, orig + b * g.orig_bstride, orig_present + b * N,
+                           rec + b * g.rec_bstride, rec_present + b * M, restored + b * g.out_bstride, s);
+        return;
+    }
+    rs::MonoMaskArgs Mo;
+    static_cast<rs::MonoCore &>(Mo) = mono_args(ctx, u, g, true, true);
+    Mo.src[0] = rs::RowMap{rec, g.rec(), high ? 0u : chunk, high ? uint32_t(M) : end};
+    Mo.src_bstride[0] = g.rec_bstride;
+    Mo.src[1] = rs::RowMap{orig, g.orig(), high ? chunk : 0u, high ? end : uint32_t(N)};
+    Mo.src_bstride[1] = g.orig_bstride;
+    Mo.nsrc = 2;
+    Mo.dst = rs::RowMap{restored, g.out(), Mo.src[1].row_begin, Mo.src[1].row_end};
+    Mo.dst_bstride = g.out_bstride;
+    Mo.fused_eval = 1;
+    Mo.low_rate = high ? 0 : 1;
+    Mo.end = end;
+    Mo.lw0 = ctx->lw0;
+    Mo.lw_fold = ctx->d_lwfold + (nd - 1);
+    // work rows that carry a shard position (decode_dev's st != 0): the erased
+    // rows of a stripe are these minus its received rows
+    const uint32_t nw = nd / 32;
+    uint32_t span[rs::kMonoFusedRows / 32] = {};
+    for (uint32_t r = 0; r < (high ? end : uint32_t(N)); ++r) span[r >> 5] |= 1u << (r & 31);
+    if (!high)
+        for (uint32_t r = chunk; r < end; ++r) span[r >> 5] |= 1u << (r & 31);
+    const uint32_t dw = rs::mask_desc_words(u);
+    const size_t bytes = size_t(g.stripes) * dw * 4;
+    uint32_t *h = reinterpret_cast<uint32_t *>(ws.h_state_pinned.get(bytes));
+    uint64_t rows = 0;  // rows the launch must read + rows it writes
+    for (uint32_t b = 0; b < g.stripes; ++b) {
+        uint32_t *d = h + size_t(b) * dw;
+        std::memset(d, 0, size_t(dw) * 4);
+        if ((d[0] = skip[b] ? 1u : 0u)) continue;
+        uint32_t rcv[rs::kMonoFusedRows / 32] = {};
+        // (received rows + missing originals = received recovery rows + N)
+        rows += put_present(rec_present + uint64_t(b) * M, uint32_t(M), high ? 0u : chunk, rcv) + N;
+        put_present(orig_present + uint64_t(b) * N, uint32_t(N), high ? chunk : 0u, rcv);
+        for (uint32_t k = 0; k < nw; ++k) {
+            uint32_t *wv = d + rs::kMaskDescHead + 8u * (k / 4) + k % 4;
+            wv[0] = span[k] & ~rcv[k];
+            wv[4] = rcv[k];
+        }
+    }
+    uint32_t *d_desc = static_cast<uint32_t *>(ws.state.get(bytes));
+    check(hipMemcpyAsync(d_desc, h, bytes, hipMemcpyHostToDevice, s));
+    ws.h_state_pinned.copied_on(s);
+    Mo.desc = d_desc;
+    Mo.desc_words = dw;
+    hipEvent_t ev = nullptr;
+    if (t_prof_ctx) prof_begin(s, &ev);
+    check(rs::launch_mono_masks(int(u), Mo, s));
+    if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), rows * uint64_t(g.packs) * 8);
 }
 
 const char *hip_msg(hipError_t e) { return hipGetErrorString(e); }
@@ -2126,6 +2234,69 @@ rs_status rs_decode_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
                        static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
                        orig_present, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride, rec_present,
                        static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride, static_cast<hipStream_t>(stream));
+        }
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                       uint64_t stripes, const void *d_orig, uint64_t orig_stride,
+                                       uint64_t orig_stripe_stride, const uint8_t *orig_present, const void *d_rec,
+                                       uint64_t rec_stride, uint64_t rec_stripe_stride, const uint8_t *rec_present,
+                                       void *d_restored, uint64_t restored_stride, uint64_t restored_stripe_stride,
+                                       uint8_t *stripe_status, void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_restored) || !orig_present || !rec_present)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        // every stripe's pattern, in stripe order, before any device work.
+        // skip: 1 = nothing missing, 2 = not decodable (status mode)
+        std::vector<uint8_t> skip(stripes, 0);
+        bool work = false;
+        for (uint64_t b = 0; b < stripes; ++b) {
+            const uint8_t *op = orig_present + b * N, *rp = rec_present + b * M;
+            uint64_t have_o = 0, have_r = 0;
+            for (uint64_t i = 0; i < N; ++i) have_o += op[i] != 0;
+            for (uint64_t i = 0; i < M; ++i) have_r += rp[i] != 0;
+            if (stripe_status) stripe_status[b] = RS_OK;
+            if (have_o + have_r < N) {
+                if (stripe_status) {
+                    stripe_status[b] = RS_ERR_NOT_ENOUGH_SHARDS;
+                    skip[b] = 2;
+                    continue;
+                }
+                set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
+                if (err) {
+                    err->original_count = N, err->original_received_count = have_o;
+                    err->recovery_received_count = have_r;
+                    err->index = b;  // the stripe (extension: the reference variant leaves index unused)
+                }
+                return RS_ERR_NOT_ENOUGH_SHARDS;
+            }
+            if (have_o == N) skip[b] = 1;
+            else work = true;
+        }
+        if (!work) return set_err(err, RS_OK);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored});
+        g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
+        if ((g.orig_bstride | g.rec_bstride | g.out_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
+        for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
+            g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
+            decode_masks_dev(ctx, sw.w, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
+                             orig_present + b0 * N, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride,
+                             rec_present + b0 * M, static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
+                             skip.data() + b0, static_cast<hipStream_t>(stream));
         }
         return set_err(err, RS_OK);
     });

@@ -287,6 +287,22 @@ struct MonoArgs : MonoCore {
 };
 // hipErrorNotSupported: no column kernel for this L (7 <= L <= 12 are built).
 hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t stream);
+// The staged batch decode with one erasure pattern PER STRIPE (k_mono_masks): the
+// patterns come from a device array of descriptors instead of the kernel arguments.
+// Descriptor of stripe b, at desc + b * desc_words (32-byte aligned, so a wave's
+// words are one aligned scalar load): word 0 = skip (the stripe's workgroups
+// return at once: nothing missing, or undecodable), words 1..7 unused, then for
+// each wave w of the workgroup (128 work rows each) 8 words: the erased bits of
+// work rows 128 w .. 128 w + 127, then their received bits (as MonoArgs::erased /
+// received).
+constexpr uint32_t kMaskDescHead = 8;
+constexpr uint32_t mask_desc_words(uint32_t L) { return kMaskDescHead + 8u * ((1u << L) / 128u); }
+struct MonoMaskArgs : MonoCore {
+    const uint32_t *desc = nullptr;
+    uint32_t desc_words = 0;
+};
+// Plain plan, fused eval_poly, grid.y = A.stripes (>= 1); 7 <= L <= 11, elems 2 or 4.
+hipError_t launch_mono_masks(int L, const MonoMaskArgs &A, hipStream_t stream);
 // Multi-chunk encodes of 2^L rows, 2 <= L <= 7 (rs_chunks.hip): HighRate (high:
 // A.chunks input chunks, images ifft_img + c * ifft_img_step, fft_img) or
 // LowRate (A.chunks output chunks, images ifft_img, fft_img + c * fft_img_step);

@@ -1754,11 +1754,18 @@ __device__ __forceinline__ gptr<T> as_global(T *p) {
 // the argument struct of a kernel variant (MonoCore unless the staged decode)
 template <int MODE, bool STAGED>
 using MonoArgT = std::conditional_t<MODE == kMonoDecode && STAGED, MonoArgs, MonoCore>;
+// MASKS (k_mono_masks): the staged batch decode whose erasure bitmaps come from
+// per-stripe descriptors in device memory (MonoMaskArgs) instead of the arguments
+template <int MODE, bool STAGED, bool MASKS>
+using MonoArgM = std::conditional_t<MASKS, MonoMaskArgs, MonoArgT<MODE, STAGED>>;
 
-template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E>
-__device__ __forceinline__ void mono_body(const MonoArgT<MODE, STAGED> &K) {
+template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, bool MASKS = false>
+__device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K) {
+    static_assert(!MASKS || (MODE == kMonoDecode && STAGED && BATCH && !SPLIT),
+                  "per-stripe patterns: the staged batch decode, plain plan");
     MonoCore A;  // the scalar arguments; the erasure bitmaps stay in K
     uint32_t ew[4] = {0, 0, 0, 0}, rw[4] = {0, 0, 0, 0};  // staged decode: the wave's bitmap words
+    uint32_t skip_stripe = 0;  // MASKS: the stripe's descriptor says skip
     {
         uint32_t packs = K.packs, ppx = K.packs_per_xcd, nsrc = K.nsrc;
         gptr<const uint8_t> b0 = as_global(K.src[0].base), b1 = as_global(K.src[1].base);
@@ -1771,7 +1778,13 @@ __device__ __forceinline__ void mono_body(const MonoArgT<MODE, STAGED> &K) {
         uint32_t ii = K.ifft_img, fi = K.fft_img, fp = K.fmt.full_packs, th = K.fmt.tail_h, iob = K.fmt.io_bytes;
         uint32_t lowr = K.low_rate, endr = K.end, lw0 = K.lw0, oh = K.out_half;
         uint64_t imw = K.img_words;
-        if constexpr (STAGED && MODE == kMonoDecode) {  // this wave's words of the erasure bitmaps
+        typedef const __attribute__((address_space(4))) uint32_t *cptr;
+        cptr desc = nullptr;
+        uint32_t desc_words = 0;
+        if constexpr (MASKS) {
+            desc = (cptr)K.desc;
+            desc_words = K.desc_words;
+        } else if constexpr (STAGED && MODE == kMonoDecode) {  // this wave's words of the erasure bitmaps
             const uint32_t w4 = 4u * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
             static_for<0, 4>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
@@ -1784,6 +1797,24 @@ __device__ __forceinline__ void mono_body(const MonoArgT<MODE, STAGED> &K) {
                      "+s"(lut), "+s"(lwf), "+s"(ii), "+s"(fi), "+s"(fp), "+s"(th), "+s"(iob), "+s"(lowr),
                      "+s"(endr), "+s"(lw0), "+s"(oh), "+s"(imw), "+s"(ew[0]), "+s"(ew[1]), "+s"(ew[2]), "+s"(ew[3]),
                      "+s"(rw[0]), "+s"(rw[1]), "+s"(rw[2]), "+s"(rw[3]));
+        if constexpr (MASKS) {
+            // the stripe's descriptor (rs_device.hpp MonoMaskArgs): its skip word and
+            // this wave's 4 + 4 bitmap words.  Constant for the kernel's lifetime and
+            // at a wave-uniform address (blockIdx.y, the wave number): scalar loads
+            // of the constant address space.  The pointer arrived with the other
+            // arguments; the loads are issued here, ahead of the lw_fold load, and
+            // waited for after it (the staged body's start): the descriptor's
+            // latency and lw_fold's overlap, both are inputs of eval_poly
+            asm volatile("" : "+s"(desc), "+s"(desc_words));
+            const cptr d = desc + uint64_t(blockIdx.y) * desc_words;
+            const cptr wv = d + kMaskDescHead + 8u * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+            skip_stripe = d[0];
+            static_for<0, 4>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                ew[i] = wv[i];
+                rw[i] = wv[4 + i];
+            });
+        }
         A.img_words = imw;
         A.packs = packs;
         A.packs_per_xcd = ppx;
@@ -1900,6 +1931,19 @@ __device__ __forceinline__ void mono_body(const MonoArgT<MODE, STAGED> &K) {
             constexpr int KP3 = G::kP3 ? (LPC * G::kP3 + 63) / 64 : 1;  // (guarded by q < LPC * kP3)
             constexpr int KSH = kSh ? (LPC * kSh + T - 1) / T : 1;  // (guarded by q < LPC * kSh)
             RS_MSTAMP(0);
+            uint32_t ebits = 0, rbits = 0, lwv = 0;
+            if constexpr (MASKS) {
+                // lw_fold (see below) goes out first; then the descriptor words, requested
+                // before it, are waited for.  A stripe with nothing to restore, or one that
+                // cannot be decoded, is left alone: its matrices are neither read nor
+                // written, and none of its waves reaches a barrier
+                lwv = reinterpret_cast<const uint32_t *>(A.lw_fold)[kEvalRemap<L> ? eval_t_pair<L>(lane, wave)
+                                                                                 : threadIdx.x];
+                asm volatile("" ::: "memory");
+                asm volatile("" : "+s"(ew[0]), "+s"(ew[1]), "+s"(ew[2]), "+s"(ew[3]), "+s"(rw[0]), "+s"(rw[1]),
+                             "+s"(rw[2]), "+s"(rw[3]), "+s"(skip_stripe));
+                if (skip_stripe) return;
+            }
             // decode: does this wave's phase-1 row block (2^IW consecutive rows) hold a
             // received row?  If not its rows are zero through phase 1: it loads no
             // rows and no phase-1 tables, and skips the phase-1 layers
@@ -1931,7 +1975,6 @@ __device__ __forceinline__ void mono_body(const MonoArgT<MODE, STAGED> &K) {
             // wait sits at the first use in col_eval_poly, after the rows and table
             // pieces are issued, and leaves those in flight while eval_poly runs
             // (vmcnt(13) in the headline decode, checked by tests/test_isa.py)
-            uint32_t ebits = 0, rbits = 0, lwv = 0;
             if constexpr (DEC) {  // the staged decode always evaluates eval_poly itself
                 const uint32_t g = lane >> 4, sh = (2u * lane) & 31u;
                 const uint32_t e0 = ew[0], e1 = ew[1], e2 = ew[2], e3 = ew[3], r0 = rw[0], r1 = rw[1], r2 = rw[2], r3 = rw[3];
@@ -1940,9 +1983,11 @@ __device__ __forceinline__ void mono_body(const MonoArgT<MODE, STAGED> &K) {
                 // lw_fold of rows 2t, 2t + 1 as one dword (the context keeps every
                 // 2^u-entry segment 4-byte aligned, rs_codec.cpp rs_context_create)
                 // (RS_MONO_EVAL_REMAP: the pair of the thread's layout-T points, col_eval_poly_remap)
-                lwv = reinterpret_cast<const uint32_t *>(A.lw_fold)[kEvalRemap<L> ? eval_t_pair<L>(lane, wave)
-                                                                                 : threadIdx.x];
-                asm volatile("" ::: "memory");  // issued first, ahead of every other load
+                if constexpr (!MASKS) {
+                    lwv = reinterpret_cast<const uint32_t *>(A.lw_fold)[kEvalRemap<L> ? eval_t_pair<L>(lane, wave)
+                                                                                     : threadIdx.x];
+                    asm volatile("" ::: "memory");  // issued first, ahead of every other load
+                }
             }
             // Decodes: a wave whose phase-1 rows hold no received row (!live) loads
             // no rows, no phase-1 tables and no scale tables (uniform branches: the
@@ -2549,6 +2594,59 @@ hipError_t launch_quad(int L, const MonoArgs &A, hipStream_t s) {
             return hipGetLastError();
         };
         return A.stripes > 1 ? go(std::true_type{}) : go(std::false_type{});
+    }
+}
+
+namespace {
+
+// The staged batch decode with per-stripe patterns: its own entry point (the
+// k_mono instantiations, and what is pinned on them, stay as they are), the
+// plain plan, MonoCore + the descriptor array as arguments.
+template <int L, int E>
+__global__ void __launch_bounds__(1 << (L - 1)) k_mono_masks(const MonoMaskArgs A) {
+    mono_body<L, 1, kMonoDecode, true, true, false, E, true>(A);
+}
+
+template <int L, int E>
+hipError_t launch_masks_le(const MonoMaskArgs &A, hipStream_t s) {
+    constexpr int LR = mono_lr(L, true);
+    static_assert(LR == 1, "k_mono_masks: 2 rows per lane");
+    using G = Stage<L, LR, mono_pk(kMonoDecode, true, false), E>;
+    size_t lds = size_t(G::words_dec) * 4;
+    if (E == 2 && lds <= 80 * 1024) lds = 84 * 1024;  // (as launch_ls)
+    static std::atomic<uint64_t> attr_devs{0};
+    if (lds > 65536) {
+        hipError_t e = lds_attr_once(attr_devs, reinterpret_cast<const void *>(&k_mono_masks<L, E>), int(lds));
+        if (e != hipSuccess) return e;
+    }
+    k_mono_masks<L, E><<<dim3(8u * A.packs_per_xcd, A.stripes), 1 << (L - LR), lds, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono_masks<%d, %d>", L, E);
+    return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_masks_l(const MonoMaskArgs &A, hipStream_t s) {
+    if constexpr (!(RS_MONO_HAS_L(L) && RS_MONO_HAS_MODE(kMonoDecode) && staged_l(L))) {
+        return hipErrorNotSupported;
+    } else {
+        return A.elems == 2 ? launch_masks_le<L, 2>(A, s) : launch_masks_le<L, 4>(A, s);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_mono_masks(int L, const MonoMaskArgs &A, hipStream_t s) {
+    if (A.packs == 0 || A.stripes == 0) return hipSuccess;
+    if (!A.desc || A.desc_words != mask_desc_words(uint32_t(L)) || A.chunks != 1 || !A.fused_eval || A.split ||
+        (A.elems != 2 && A.elems != 4))
+        return hipErrorInvalidValue;
+    switch (L) {
+        case 7: return launch_masks_l<7>(A, s);
+        case 8: return launch_masks_l<8>(A, s);
+        case 9: return launch_masks_l<9>(A, s);
+        case 10: return launch_masks_l<10>(A, s);
+        case 11: return launch_masks_l<11>(A, s);
+        default: return hipErrorNotSupported;
     }
 }
 
