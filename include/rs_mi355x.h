@@ -278,6 +278,65 @@ rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t o
                                        void *d_restored, uint64_t restored_stride, uint64_t restored_stripe_stride,
                                        uint8_t *stripe_status, void *stream, rs_error *err);
 
+/* ---- repair: the whole stripe back, recovery shards included ----
+ * (MI355X extension: a node that lost a disk has lost recovery shards too, and
+ * the stripe stays degraded until they are rebuilt.)  A decode that also
+ * restores the missing RECOVERY shards, in about the time of the decode: after
+ * the decode's last FFT every erased position of the codeword holds its value
+ * times the error locator, the recovery positions included, so the reveal
+ * multiply that restores an original restores a recovery shard as well
+ * (DESIGN.md "Repair") -- no second transform, no gather, no scratch matrix.
+ *   Arguments: those of the matching rs_decode_device* call, plus d_recovery_out
+ * (recovery_count rows; row / stripe strides as for the other matrices, 0 =
+ * shard_bytes / recovery_count rows) between d_restored... and stream.
+ *   Contract: missing originals are written to d_restored exactly as by the
+ * decode call; missing recovery shard i is written to row i of d_recovery_out,
+ * byte-identical to the encoder's recovery shard (block and tail layout of
+ * rs_encode_device).  Present rows of either output are never written, absent
+ * rows of either input never read.  Unaligned bases or strides take the
+ * byte-wise path, as everywhere.
+ *   In place: d_recovery_out may be d_recovery (same stride) and d_restored may
+ * be d_original -- the natural way to heal a stripe: the holes are filled,
+ * nothing else moves.  Safe by construction: the rows written are exactly the
+ * rows never read.
+ *   Errors, all before any device work, in rs_decode_device_strided's order:
+ * null context / pointers (d_recovery_out included) -> RS_ERR_INVALID_ARGUMENT,
+ * then rs_validate, then the strides, then NotEnoughShards with its counts
+ * (fewer than original_count shards present in total).
+ *   Unlike the decode the call does not return early when no original is
+ * missing: missing recovery shards alone are rebuilt.  When they form one run
+ * of consecutive rows the call runs the encode with its destination narrowed
+ * to that run (measured about twice as fast as the decode's kernels there:
+ * DESIGN.md "Repair"); any other pattern takes the decode's kernels.  Either
+ * way only missing rows are written.  With nothing missing at all it returns
+ * RS_OK, launches nothing and writes nothing.  With no recovery shard missing
+ * it is the decode call, launch for launch.
+ *   rs_repair_device_batch applies ONE pattern to every stripe, like
+ * rs_decode_device_batch, and runs as one launch where that call does.
+ * Asynchronous on `stream`; scratch per (context, stream); profile records as
+ * the decode's, the bytes of a launch counting the recovery rows it writes.
+ *   Not covered yet (each can follow now that the kernels take a second
+ * destination): per-stripe patterns (rs_decode_device_batch_masks), the
+ * host-memory pipeline (rs_decode_host), the rs_decoder object API and the
+ * sharded multi-device decoder. */
+rs_status rs_repair_device(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                           uint64_t shard_bytes, const void *d_original, const uint8_t *original_present,
+                           const void *d_recovery, const uint8_t *recovery_present, void *d_restored,
+                           void *d_recovery_out, void *stream, rs_error *err);
+rs_status rs_repair_device_strided(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                   uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
+                                   const uint8_t *original_present, const void *d_recovery, uint64_t recovery_stride,
+                                   const uint8_t *recovery_present, void *d_restored, uint64_t restored_stride,
+                                   void *d_recovery_out, uint64_t recovery_out_stride, void *stream, rs_error *err);
+rs_status rs_repair_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                 uint64_t shard_bytes, uint64_t stripes, const void *d_original,
+                                 uint64_t original_stride, uint64_t original_stripe_stride,
+                                 const uint8_t *original_present, const void *d_recovery, uint64_t recovery_stride,
+                                 uint64_t recovery_stripe_stride, const uint8_t *recovery_present, void *d_restored,
+                                 uint64_t restored_stride, uint64_t restored_stripe_stride, void *d_recovery_out,
+                                 uint64_t recovery_out_stride, uint64_t recovery_out_stripe_stride, void *stream,
+                                 rs_error *err);
+
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x
  * shard_bytes) are row-major HOST matrices; pinned memory (rs_host_alloc,

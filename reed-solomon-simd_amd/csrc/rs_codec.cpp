@@ -493,14 +493,16 @@ struct Geom {
     uint64_t stride;
     uint32_t packs;
     uint64_t orig_stride = 0, rec_stride = 0, out_stride = 0;
+    uint64_t out2_stride = 0;  // repair: the recovery output matrix
     // a batch of stripes of this shape: stripe b's matrices start b * *_bstride
     // bytes after the base pointers (rs_encode_device_batch / rs_decode_device_batch)
     uint32_t stripes = 1;
-    uint64_t orig_bstride = 0, rec_bstride = 0, out_bstride = 0;
+    uint64_t orig_bstride = 0, rec_bstride = 0, out_bstride = 0, out2_bstride = 0;
     rs::ShardFormat fmt;  // byte layout of the caller's matrices (tails, alignment)
     uint64_t orig() const { return orig_stride ? orig_stride : stride; }
     uint64_t rec() const { return rec_stride ? rec_stride : stride; }
     uint64_t out() const { return out_stride ? out_stride : stride; }
+    uint64_t out2() const { return out2_stride ? out2_stride : stride; }
 };
 
 // Packs of a shard of S bytes: 8 per whole 64-byte block, then one per 4
@@ -512,12 +514,14 @@ uint32_t packs_of(uint64_t S) { return uint32_t(S / 64 * 8 + ((S % 64) / 2 + 3) 
 // src/engine/shards.rs:38-74; rs_device.hpp ShardFormat).  Strides 0 = S.
 // Work buffers use rows of whole 64-byte blocks.
 Geom device_geom(uint64_t S, uint64_t orig_stride, uint64_t rec_stride, uint64_t out_stride,
-                 std::initializer_list<const void *> ptrs) {
+                 std::initializer_list<const void *> ptrs, uint64_t out2_stride = 0) {
     Geom g{round_up(S, 64), packs_of(S)};
     g.orig_stride = orig_stride ? orig_stride : S;
     g.rec_stride = rec_stride ? rec_stride : S;
     g.out_stride = out_stride ? out_stride : S;
-    bool aligned = g.orig_stride % 4 == 0 && g.rec_stride % 4 == 0 && g.out_stride % 4 == 0;
+    g.out2_stride = out2_stride ? out2_stride : S;
+    bool aligned = g.orig_stride % 4 == 0 && g.rec_stride % 4 == 0 && g.out_stride % 4 == 0 &&
+                   g.out2_stride % 4 == 0;
     for (const void *p : ptrs) aligned = aligned && (reinterpret_cast<uintptr_t>(p) & 3) == 0;
     if (S % 64 || !aligned) {
         g.fmt.full_packs = uint32_t(S / 64 * 8);
@@ -764,6 +768,13 @@ void launch_mono(int mode, uint32_t L, const rs::MonoArgs &M, hipStream_t s, uin
     if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), bytes);
 }
 
+void launch_mono_repair(uint32_t L, const rs::MonoArgs2 &M, hipStream_t s, uint64_t bytes) {
+    hipEvent_t ev = nullptr;
+    if (t_prof_ctx) prof_begin(s, &ev);
+    check(rs::launch_mono_repair(int(L), M, s));
+    if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), bytes);
+}
+
 // A single-chunk encode goes to the lane kernel (rs_lane.hip) when enabled and
 // its column arguments are 2-element packs of 2^8..2^10 rows; false: not taken.
 bool try_lane(rs_context *ctx, uint32_t L, uint32_t chunks, const rs::MonoArgs &M, hipStream_t s, uint64_t bytes) {
@@ -859,10 +870,19 @@ const uint32_t *top_table(rs_context *ctx, uint32_t delta, uint32_t elems) {
     const uint32_t j = delta / 2048;
     return elems == 2 ? ctx->d_top + kTopTables * rs::kPermWords + j * rs::kPerm2Words : ctx->d_top + j * rs::kPermWords;
 }
-void launch_half(int mode, uint32_t halves, const rs::MonoArgs &M, hipStream_t s, uint64_t bytes) {
+// dst2 (repair, kMonoHalfFDec): the second destination map
+void launch_half(int mode, uint32_t halves, const rs::MonoArgs &M, hipStream_t s, uint64_t bytes,
+                 const rs::RowMap *dst2 = nullptr) {
     hipEvent_t ev = nullptr;
     if (t_prof_ctx) prof_begin(s, &ev);
-    check(rs::launch_mono_half(mode, halves, M, s));
+    if (dst2) {
+        rs::MonoArgs2 M2;
+        static_cast<rs::MonoArgs &>(M2) = M;
+        M2.dst2 = *dst2;
+        check(rs::launch_mono_half_repair(halves, M2, s));
+    } else {
+        check(rs::launch_mono_half(mode, halves, M, s));
+    }
     if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), bytes);
 }
 // in_halves / out_halves: bit h = half h holds input rows (received rows) /
@@ -870,7 +890,8 @@ void launch_half(int mode, uint32_t halves, const rs::MonoArgs &M, hipStream_t s
 // FFT's skew offset; rowinfo (decodes): eval_poly's output for the 4096 rows.
 void half_split(rs_context *ctx, Workspace &ws, const Geom &g, bool dec, uint32_t i_delta, uint32_t f_delta,
                 const rs::RowMap *src, uint32_t nsrc, const rs::RowMap &dst, const uint32_t *rowinfo,
-                uint32_t in_halves, uint32_t out_halves, uint64_t in_rows, uint64_t out_rows, hipStream_t s) {
+                uint32_t in_halves, uint32_t out_halves, uint64_t in_rows, uint64_t out_rows, hipStream_t s,
+                const rs::RowMap *dst2 = nullptr) {
     if (!in_halves || !out_halves) return;
     uint8_t *W = static_cast<uint8_t *>(ws.buf[0].get(size_t(4096) * g.stride));
     Geom g2 = g;
@@ -898,7 +919,7 @@ void half_split(rs_context *ctx, Workspace &ws, const Geom &g, bool dec, uint32_
     F.fft_img = f_delta / 2048;
     F.fft_img_step = 1;
     F.out_half = out_halves == 2 ? 1 : 0;
-    launch_half(dec ? rs::kMonoHalfFDec : rs::kMonoHalfFEnc, nout, F, s, (2048 * nin + out_rows) * row);
+    launch_half(dec ? rs::kMonoHalfFDec : rs::kMonoHalfFEnc, nout, F, s, (2048 * nin + out_rows) * row, dst2);
 }
 // halves of [b, e) in a 4096-row transform
 uint32_t halves_of(uint64_t b, uint64_t e) { return b >= e ? 0u : (b < 2048 ? 1u : 0u) | (e > 2048 ? 2u : 0u); }
@@ -920,22 +941,27 @@ bool chunk_parallel(rs_context *ctx, const Geom &g, uint64_t scratch = 0) {
 // HighRate encode (rate_high.rs:44-87) from device rows to device rows:
 // chunk c's IFFT uses skew_delta c*n + n, the chunks are XOR-folded, one FFT
 // with skew_delta 0 produces the recovery rows.
+// [out_lo, out_hi): the recovery rows to store (default: all) -- every kernel
+// stores the rows of its destination map only, so a narrower map is a
+// row-filtered encode (a repair that misses one run of recovery rows).
 void encode_high(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint64_t M, const uint8_t *orig,
-                 uint8_t *rec, hipStream_t s) {
+                 uint8_t *rec, hipStream_t s, uint32_t out_lo = 0, uint32_t out_hi = ~0u) {
+    out_hi = uint32_t(std::min<uint64_t>(out_hi, M));
+    out_lo = std::min(out_lo, out_hi);
     const uint32_t n = uint32_t(next_pow2(M)), L = ilog2(n);
     const uint32_t C = uint32_t((N + n - 1) / n);
     if (g.stripes > 1 && !(use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C))) {  // batch: one stripe after another
         Geom g1 = g;
         g1.stripes = 1;
         for (uint32_t b = 0; b < g.stripes; ++b)
-            encode_high(ctx, ws, g1, N, M, orig + b * g.orig_bstride, rec + b * g.rec_bstride, s);
+            encode_high(ctx, ws, g1, N, M, orig + b * g.orig_bstride, rec + b * g.rec_bstride, s, out_lo, out_hi);
         return;
     }
     const Levels lv = levels(L, max_k_enc(g.packs));
     rs::PassArgs A = base_args(ctx, g, n);
     A.ifft_delta = n;
     A.ifft_delta_step = n;
-    const rs::RowMap src{orig, g.orig(), 0, uint32_t(N)}, dst{rec, g.rec(), 0, uint32_t(M)};
+    const rs::RowMap src{orig, g.orig(), 0, uint32_t(N)}, dst{rec + uint64_t(out_lo) * g.rec(), g.rec(), out_lo, out_hi};
     if (use_mono(ctx, L, g, C)) {
         rs::MonoArgs Mo = mono_args(ctx, L, g, rs::mono_staged(int(L), C));
         Mo.src[0] = src;
@@ -947,17 +973,18 @@ void encode_high(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint
         Mo.ifft_img = 1;  // chunk c: skew offset c * n + n
         Mo.ifft_img_step = 1;
         Mo.fft_img = 0;
-        const uint64_t bytes = (N + M) * uint64_t(g.packs) * 8 * g.stripes;
+        const uint64_t bytes = (N + out_hi - out_lo) * uint64_t(g.packs) * 8 * g.stripes;
         if (!try_quad(ctx, L, C, Mo, s, bytes) && !try_lane(ctx, L, C, Mo, s, bytes))
             launch_mono(rs::kMonoEncodeHigh, L, Mo, s, bytes);
         return;
     }
     if (use_chunks(ctx, L, g, C, true)) {
-        launch_chunks(ctx, g, true, L, src, dst, C, (N + M) * uint64_t(g.packs) * 8, s);
+        launch_chunks(ctx, g, true, L, src, dst, C, (N + out_hi - out_lo) * uint64_t(g.packs) * 8, s);
         return;
     }
     if (use_half(ctx, L, g, C)) {  // IFFT skew n, FFT skew 0
-        half_split(ctx, ws, g, false, n, 0, &src, 1, dst, nullptr, halves_of(0, N), halves_of(0, M), N, M, s);
+        half_split(ctx, ws, g, false, n, 0, &src, 1, dst, nullptr, halves_of(0, N), halves_of(out_lo, out_hi), N,
+                   out_hi - out_lo, s);
         return;
     }
     if (lv.m == 1 && (C == 1 || !chunk_parallel(ctx, g, uint64_t(C) * n * g.stride))) {
@@ -1013,22 +1040,25 @@ void encode_high(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint
 
 // LowRate encode (rate_low.rs:44-87): one IFFT (skew 0), then output chunk c
 // is FFT'd with skew_delta c*n + n.
+// [out_lo, out_hi): as encode_high.
 void encode_low(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint64_t M, const uint8_t *orig,
-                uint8_t *rec, hipStream_t s) {
+                uint8_t *rec, hipStream_t s, uint32_t out_lo = 0, uint32_t out_hi = ~0u) {
+    out_hi = uint32_t(std::min<uint64_t>(out_hi, M));
+    out_lo = std::min(out_lo, out_hi);
     const uint32_t n = uint32_t(next_pow2(N)), L = ilog2(n);
     const uint32_t C = uint32_t((M + n - 1) / n);
     if (g.stripes > 1 && !(use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C))) {  // batch: one stripe after another
         Geom g1 = g;
         g1.stripes = 1;
         for (uint32_t b = 0; b < g.stripes; ++b)
-            encode_low(ctx, ws, g1, N, M, orig + b * g.orig_bstride, rec + b * g.rec_bstride, s);
+            encode_low(ctx, ws, g1, N, M, orig + b * g.orig_bstride, rec + b * g.rec_bstride, s, out_lo, out_hi);
         return;
     }
     const Levels lv = levels(L, max_k_enc(g.packs));
     rs::PassArgs A = base_args(ctx, g, n);
     A.fft_delta = n;
     A.fft_delta_step = n;
-    const rs::RowMap src{orig, g.orig(), 0, uint32_t(N)}, dst{rec, g.rec(), 0, uint32_t(M)};
+    const rs::RowMap src{orig, g.orig(), 0, uint32_t(N)}, dst{rec + uint64_t(out_lo) * g.rec(), g.rec(), out_lo, out_hi};
     if (use_mono(ctx, L, g, C)) {
         rs::MonoArgs Mo = mono_args(ctx, L, g, rs::mono_staged(int(L), C));
         Mo.src[0] = src;
@@ -1040,17 +1070,18 @@ void encode_low(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint6
         Mo.ifft_img = 0;
         Mo.fft_img = 1;  // output chunk c: skew offset c * n + n
         Mo.fft_img_step = 1;
-        const uint64_t bytes = (N + M) * uint64_t(g.packs) * 8 * g.stripes;
+        const uint64_t bytes = (N + out_hi - out_lo) * uint64_t(g.packs) * 8 * g.stripes;
         if (!try_quad(ctx, L, C, Mo, s, bytes) && !try_lane(ctx, L, C, Mo, s, bytes))
             launch_mono(rs::kMonoEncodeLow, L, Mo, s, bytes);
         return;
     }
     if (use_chunks(ctx, L, g, C, false)) {
-        launch_chunks(ctx, g, false, L, src, dst, C, (N + M) * uint64_t(g.packs) * 8, s);
+        launch_chunks(ctx, g, false, L, src, dst, C, (N + out_hi - out_lo) * uint64_t(g.packs) * 8, s);
         return;
     }
     if (use_half(ctx, L, g, C)) {  // IFFT skew 0, FFT skew n
-        half_split(ctx, ws, g, false, 0, n, &src, 1, dst, nullptr, halves_of(0, N), halves_of(0, M), N, M, s);
+        half_split(ctx, ws, g, false, 0, n, &src, 1, dst, nullptr, halves_of(0, N), halves_of(out_lo, out_hi), N,
+                   out_hi - out_lo, s);
         return;
     }
     if (lv.m == 1) {
@@ -1171,10 +1202,22 @@ std::vector<uint64_t> count_per_block(const std::vector<uint8_t> &st, uint32_t n
     return c;
 }
 
+// Erased rows of the output range per 2^sb_log-row superblock: the restored
+// originals' rows (out) and, in a repair, the missing recovery rows (out2;
+// nullptr in a decode).  HighRate's padding rows [M, chunk) lie in neither.
+std::vector<uint64_t> erased_out_per_block(const std::vector<uint8_t> &st, uint32_t nd, uint32_t sb_log,
+                                           const rs::RowMap &out, const rs::RowMap *out2) {
+    std::vector<uint64_t> c = count_per_block(st, nd, sb_log, out.row_begin, out.row_end, 1);
+    if (out2) {
+        const std::vector<uint64_t> c2 = count_per_block(st, nd, sb_log, out2->row_begin, out2->row_end, 1);
+        for (size_t i = 0; i < c.size(); ++i) c[i] += c2[i];
+    }
+    return c;
+}
+
 void fft_pass_pruned(rs::PassArgs P, const Levels &lv, uint32_t k, uint32_t nd, const std::vector<uint8_t> &st,
-                     const rs::RowMap &out, hipStream_t s) {
-    launch_runs(P, lv, k, rs::kFft, count_per_block(st, nd, lv.lo[k] + lv.K[k], out.row_begin, out.row_end, 1), s,
-                true);
+                     const rs::RowMap &out, const rs::RowMap *out2, hipStream_t s) {
+    launch_runs(P, lv, k, rs::kFft, erased_out_per_block(st, nd, lv.lo[k] + lv.K[k], out, out2), s, true);
 }
 
 // Work rows of a decode: the second shard kind starts at row `chunk`, the last
@@ -1202,13 +1245,23 @@ DecodeRows decode_rows(rs_context *ctx, bool high, const Geom &g, uint64_t N, ui
 // Decode (rate_high.rs:172-254 / rate_low.rs:172-254).  Only missing original
 // rows of `restored` are written.
 //
+// Repair (rec_out != nullptr; rs_repair_device*): the missing recovery rows are
+// written to rec_out as well.  After the last FFT every erased position of the
+// codeword holds its value times the error locator, the recovery positions
+// included, so the reveal multiply of an erased recovery row gives the recovery
+// shard (DESIGN.md "Repair").  The kernels take a second destination map over the
+// recovery rows' work rows; every plan that depends on where the outputs lie (the
+// narrowed spans, the split plan, out_h, the pruned FFT passes) counts the erased
+// rows of both maps.  With no recovery row missing this is the decode, launch for
+// launch.
+//
 // Multi-level formal derivative (DESIGN.md "Formal derivative across passes"):
 // with X_k the IFFT output after levels 0..k and P_(k) the derivative terms of
 // level k's bits,  U = F_top(P_(top) X_top),  V_{m-2} = F_{m-2}((I + P_(m-2)) X_{m-2} + U),
 // V_k = F_k(P_(k) X_k + V_{k+1}) for k < m-2, and V_0 is FFT(derivative(IFFT)).
 void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64_t N, uint64_t M,
                 const uint8_t *orig, const uint8_t *orig_present, const uint8_t *rec, const uint8_t *rec_present,
-                uint8_t *restored, hipStream_t s) {
+                uint8_t *restored, hipStream_t s, uint8_t *rec_out = nullptr) {
     const DecodeRows dr = decode_rows(ctx, high, g, N, M);
     const uint32_t chunk = dr.chunk, end = dr.end, nd = dr.nd, u = dr.u;
     // erasure vector + received flags per work row
@@ -1228,6 +1281,14 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
     const rs::RowMap rec_map{rec, g.rec(), high ? 0u : chunk, high ? uint32_t(M) : end};
     const rs::RowMap orig_map{orig, g.orig(), high ? chunk : 0u, high ? end : uint32_t(N)};
     const rs::RowMap out_map{restored, g.out(), orig_map.row_begin, orig_map.row_end};
+    // repair: the recovery rows' destination, when one of them is missing
+    uint64_t missing_rec = 0;
+    if (rec_out)
+        for (uint64_t i = 0; i < M; ++i) missing_rec += !rec_present[i];
+    const bool two = missing_rec != 0;
+    const rs::RowMap out2_map{rec_out, g.out2(), rec_map.row_begin, rec_map.row_end};
+    const rs::RowMap *const out2 = two ? &out2_map : nullptr;
+    missing += missing_rec;  // (rows written: the profiler's byte counts)
     const bool mono = use_mono(ctx, u, g, 1);
     const bool fused = mono && rs::mono_staged(int(u), 1) && nd <= rs::kMonoFusedRows;
     if (g.stripes > 1 && !fused) {  // batch: one stripe after another
@@ -1235,12 +1296,13 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         g1.stripes = 1;
         for (uint32_t b = 0; b < g.stripes; ++b)
             decode_dev(ctx, ws, high, g1, N, M, orig + b * g.orig_bstride, orig_present, rec + b * g.rec_bstride,
-                       rec_present, restored + b * g.out_bstride, s);
+                       rec_present, restored + b * g.out_bstride, s, two ? rec_out + b * g.out2_bstride : nullptr);
         return;
     }
     if (fused) {
         // one launch: every column workgroup evaluates eval_poly itself
-        rs::MonoArgs Mo = mono_args(ctx, u, g, true, true);
+        rs::MonoArgs2 Mo;
+        static_cast<rs::MonoArgs &>(Mo) = mono_args(ctx, u, g, true, true);
         Mo.src[0] = rec_map;
         Mo.src_bstride[0] = g.rec_bstride;
         Mo.src[1] = orig_map;
@@ -1252,15 +1314,20 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         // runs the FFT's last in-wave layers, the reveal multiply and the stores
         // instead of the 8 of the restored half (VALU accounting,
         // profiles/r06c/valu_account.txt); present rows are never written either way
-        {
-            uint32_t lo = out_map.row_end, hi = out_map.row_begin;
-            for (uint32_t r = out_map.row_begin; r < out_map.row_end; ++r)
+        // (repair: each map narrowed to its own erased rows; a map without any is empty)
+        auto narrowed = [&](const rs::RowMap &m, bool or_empty) {
+            uint32_t lo = m.row_end, hi = m.row_begin;
+            for (uint32_t r = m.row_begin; r < m.row_end; ++r)
                 if (st[r] == 1) lo = std::min(lo, r), hi = r + 1;
-            Mo.dst = lo < hi ? rs::RowMap{out_map.base + uint64_t(lo - out_map.row_begin) * out_map.stride,
-                                          out_map.stride, lo, hi}
-                             : out_map;
-        }
+            if (lo < hi) return rs::RowMap{m.base + uint64_t(lo - m.row_begin) * m.stride, m.stride, lo, hi};
+            return or_empty ? rs::RowMap{m.base, m.stride, 0, 0} : m;
+        };
+        Mo.dst = narrowed(out_map, two);
         Mo.dst_bstride = g.out_bstride;
+        if (two) {
+            Mo.dst2 = narrowed(out2_map, true);
+            Mo.dst2_bstride = g.out2_bstride;
+        }
         Mo.fused_eval = 1;
         Mo.low_rate = high ? 0 : 1;
         Mo.end = end;
@@ -1274,15 +1341,22 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         // equal at 2^10, the split plan faster at 2^11: profiles/r04a/split_ab.txt)
         if (ctx->split && rs::mono_split(int(u)) && u >= 10) {
             // split plan: every restored row in one half of the work rows
+            // (repair: the missing recovery rows are outputs too -- a HighRate repair
+            // with losses of both kinds has outputs in both halves: no split)
             bool lower = false, upper = false;
             for (uint32_t r = out_map.row_begin; r < out_map.row_end; ++r)
                 if (st[r] == 1) (r < nd / 2 ? lower : upper) = true;
+            if (two)
+                for (uint32_t r = out2_map.row_begin; r < out2_map.row_end; ++r)
+                    if (st[r] == 1) (r < nd / 2 ? lower : upper) = true;
             if (!(lower && upper)) {
                 Mo.split = 1;
                 Mo.out_half = upper ? 1 : 0;
             }
         }
-        launch_mono(rs::kMonoDecode, u, Mo, s, (received + missing) * uint64_t(g.packs) * 8 * g.stripes);
+        const uint64_t bytes = (received + missing) * uint64_t(g.packs) * 8 * g.stripes;
+        if (two) launch_mono_repair(u, Mo, s, bytes);
+        else launch_mono(rs::kMonoDecode, u, Mo, s, bytes);
         return;
     }
     if (!mono && nd <= rs::kPassEvalRows && levels(u, max_k_dec(u, g.packs)).m == 1) {
@@ -1295,6 +1369,7 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         A.load_scale = 1;
         A.fd_mode = 2;
         A.dst = out_map;
+        if (two) A.dst2 = out2_map;
         A.reveal = 1;
         A.fused_eval = 1;
         A.ev_low_rate = high ? 0 : 1;
@@ -1339,20 +1414,28 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         uint32_t in_h = 0, out_h = 0;
         for (uint32_t r = 0; r < nd; ++r) in_h |= uint32_t(st[r] == 2) << (r >> 11);
         for (uint32_t r = out_map.row_begin; r < out_map.row_end; ++r) out_h |= uint32_t(st[r] == 1) << (r >> 11);
+        if (two)
+            for (uint32_t r = out2_map.row_begin; r < out2_map.row_end; ++r) out_h |= uint32_t(st[r] == 1) << (r >> 11);
         const rs::RowMap src[2] = {rec_map, orig_map};
-        half_split(ctx, ws, g, true, 0, 0, src, 2, out_map, d_rowinfo, in_h, out_h, received, missing, s);
+        half_split(ctx, ws, g, true, 0, 0, src, 2, out_map, d_rowinfo, in_h, out_h, received, missing, s, out2);
         return;
     }
     rs::PassArgs A = base_args(ctx, g, nd);
     A.rowinfo = d_rowinfo;
     if (mono) {
-        rs::MonoArgs Mo = mono_args(ctx, u, g, false);
+        rs::MonoArgs2 Mo;
+        static_cast<rs::MonoArgs &>(Mo) = mono_args(ctx, u, g, false);
         Mo.src[0] = rec_map;
         Mo.src[1] = orig_map;
         Mo.nsrc = 2;
         Mo.dst = out_map;
         Mo.rowinfo = d_rowinfo;
-        launch_mono(rs::kMonoDecode, u, Mo, s, (received + missing) * uint64_t(g.packs) * 8);
+        if (two) {
+            Mo.dst2 = out2_map;
+            launch_mono_repair(u, Mo, s, (received + missing) * uint64_t(g.packs) * 8);
+        } else {
+            launch_mono(rs::kMonoDecode, u, Mo, s, (received + missing) * uint64_t(g.packs) * 8);
+        }
         return;
     }
     const Levels lv = levels(u, max_k_dec(u, g.packs));
@@ -1363,6 +1446,7 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         A.load_scale = 1;
         A.fd_mode = 2;
         A.dst = out_map;
+        if (two) A.dst2 = out2_map;
         A.reveal = 1;
         run_level(A, lv, 0, rs::kIfft | rs::kFft, nd, s, received, missing);
         return;
@@ -1409,7 +1493,7 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         // U stores are skipped per row only where rows are long enough for the
         // saved write to outweigh the per-row test (measured, profiles/r01o)
         if (uint64_t(g.packs) * 8 >= kKeepOutRowBytes) {
-            const std::vector<uint64_t> keep_blk = count_per_block(st, nd, G, out_map.row_begin, out_map.row_end, 1);
+            const std::vector<uint64_t> keep_blk = erased_out_per_block(st, nd, G, out_map, out2);
             for (uint32_t b = 0; b < keep_blk.size(); ++b)
                 if (!keep_blk[b]) A.keep_out[b >> 6] &= ~(1ull << (b & 63));
         }
@@ -1447,7 +1531,7 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
     // (RS_MI355X_BFLY_PRUNE=0: off, A/B)
     static const bool bfly_prune = !getenv("RS_MI355X_BFLY_PRUNE") || getenv("RS_MI355X_BFLY_PRUNE")[0] != '0';
     if (bfly_prune && masks && lv.K[lv.m - 1] <= 6) {
-        const std::vector<uint64_t> need = count_per_block(st, nd, G, out_map.row_begin, out_map.row_end, 1);
+        const std::vector<uint64_t> need = erased_out_per_block(st, nd, G, out_map, out2);
         T.bfly_prune = 1;
         T.zin_local = top_masks ? A.zero_in[0] : 0;
         T.need_local = 0;
@@ -1464,11 +1548,12 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
         P.xor_in = U;
         if (k == 0) {
             P.dst = out_map;
+            if (two) P.dst2 = out2_map;
             P.reveal = 1;
         } else {
             P.work_out = U;
         }
-        fft_pass_pruned(P, lv, uint32_t(k), nd, st, out_map, s);
+        fft_pass_pruned(P, lv, uint32_t(k), nd, st, out_map, out2, s);
     }
 }
 
@@ -2237,6 +2322,99 @@ rs_status rs_decode_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
         }
         return set_err(err, RS_OK);
     });
+}
+
+// ---- repair: the decode + the missing recovery shards (include/rs_mi355x.h) ----
+
+rs_status rs_repair_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, uint64_t stripes,
+                                 const void *d_orig, uint64_t orig_stride, uint64_t orig_stripe_stride,
+                                 const uint8_t *orig_present, const void *d_rec, uint64_t rec_stride,
+                                 uint64_t rec_stripe_stride, const uint8_t *rec_present, void *d_restored,
+                                 uint64_t restored_stride, uint64_t restored_stripe_stride, void *d_recovery_out,
+                                 uint64_t recovery_out_stride, uint64_t recovery_out_stripe_stride, void *stream,
+                                 rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_restored) || !ptr_ok(d_recovery_out) ||
+        !orig_present || !rec_present)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S) ||
+        !stride_ok(recovery_out_stride, S))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    uint64_t have_o = 0, have_r = 0;
+    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
+    for (uint64_t i = 0; i < M; ++i) have_r += rec_present[i] != 0;
+    if (have_o + have_r < N) {
+        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
+        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = have_r;
+        return RS_ERR_NOT_ENOUGH_SHARDS;
+    }
+    // nothing missing: nothing launched, nothing written, the context not touched.
+    // Missing recovery shards alone still run (the decode returns here for them).
+    if ((have_o == N && have_r == M) || stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored, d_recovery_out},
+                             recovery_out_stride);
+        g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
+        g.out2_bstride = recovery_out_stripe_stride ? recovery_out_stripe_stride : M * g.out2();
+        if (stripes > 1 && (g.orig_bstride | g.rec_bstride | g.out_bstride | g.out2_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
+        // Every original present and the missing recovery rows one run [lo, hi): the
+        // encode with its destination narrowed to that run -- every encode kernel stores
+        // only the rows of its destination map -- is about twice as fast as the decode's
+        // kernels (1024:1024 x 1 KiB, one shard: 8.3 vs 15.3 us; 64 stripes 223 vs 493 us,
+        // profiles/repair/repair_time_decode_route.txt).  Each further run would cost one
+        // more encode, which is the decode route's time for ANY pattern: those, and
+        // every repair with an original missing, take the decode's kernels.
+        uint32_t lo = 0, hi = 0, runs = 0;
+        if (have_o == N)
+            for (uint32_t i = 0; i < M; ++i)
+                if (!rec_present[i]) {
+                    if (runs == 0 || i != hi) ++runs, lo = runs == 1 ? i : lo;
+                    hi = i + 1;
+                }
+        const bool by_encode = have_o == N && runs == 1;
+        Geom ge = g;  // the encode's recovery matrix is d_recovery_out
+        ge.rec_stride = g.out2_stride;
+        ge.rec_bstride = g.out2_bstride;
+        for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
+            g.stripes = ge.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
+            const uint8_t *o = static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride;
+            uint8_t *y = static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride;
+            if (by_encode) {
+                if (high) encode_high(ctx, sw.w, ge, N, M, o, y, static_cast<hipStream_t>(stream), lo, hi);
+                else encode_low(ctx, sw.w, ge, N, M, o, y, static_cast<hipStream_t>(stream), lo, hi);
+                continue;
+            }
+            decode_dev(ctx, sw.w, high, g, N, M, o, orig_present,
+                       static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride, rec_present,
+                       static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride, static_cast<hipStream_t>(stream), y);
+        }
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_repair_device_strided(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                   const void *d_orig, uint64_t orig_stride, const uint8_t *orig_present,
+                                   const void *d_rec, uint64_t rec_stride, const uint8_t *rec_present,
+                                   void *d_restored, uint64_t restored_stride, void *d_recovery_out,
+                                   uint64_t recovery_out_stride, void *stream, rs_error *err) {
+    return rs_repair_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, orig_present, d_rec, rec_stride, 0,
+                                  rec_present, d_restored, restored_stride, 0, d_recovery_out, recovery_out_stride, 0,
+                                  stream, err);
+}
+
+rs_status rs_repair_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const void *d_orig,
+                           const uint8_t *orig_present, const void *d_rec, const uint8_t *rec_present,
+                           void *d_restored, void *d_recovery_out, void *stream, rs_error *err) {
+    return rs_repair_device_strided(ctx, rate, N, M, S, d_orig, 0, orig_present, d_rec, 0, rec_present, d_restored, 0,
+                                    d_recovery_out, 0, stream, err);
 }
 
 rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,

@@ -169,6 +169,11 @@ struct PassArgs {
     // below read only the needed blocks' rows)
     uint32_t bfly_prune = 0;
     uint64_t zin_local = 0, need_local = ~0ull;
+
+    // ---- repair (reveal = 1 only): a second destination over the recovery rows'
+    // work-row range, disjoint from dst; empty (row_end = 0) in every decode, whose
+    // reveal stores test it with one uniform compare and never enter it
+    RowMap dst2;
 };
 constexpr uint32_t kPassEvalRows = 64;
 
@@ -287,6 +292,22 @@ struct MonoArgs : MonoCore {
 };
 // hipErrorNotSupported: no column kernel for this L (7 <= L <= 12 are built).
 hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t stream);
+// Repair (rs_repair_device*): the decode kernels with a second destination map,
+// dst2 over the recovery rows' work-row range (dst: the originals').  A row is
+// stored to the map that holds it when it is erased; rows of neither map (the
+// HighRate padding [M, chunk)) stay unwritten.  Either map may be empty
+// (row_begin = row_end = 0).  These are instantiations of their own
+// (k_mono_repair, built in rs_repair.hip from rs_mono.hip's body): the decode's
+// kernels and their arguments stay as they are.
+struct MonoArgs2 : MonoArgs {
+    RowMap dst2;
+    uint64_t dst2_bstride = 0;
+};
+// kMonoDecode: the staged fused-eval_poly kernel (7 <= L <= 11; plain or split
+// plan, stripes >= 1 as grid.y) or the unstaged one (L = 12, rowinfo).
+hipError_t launch_mono_repair(int L, const MonoArgs2 &A, hipStream_t stream);
+// kMonoHalfFDec with two destinations (launch_mono_half's second launch).
+hipError_t launch_mono_half_repair(uint32_t halves, const MonoArgs2 &A, hipStream_t stream);
 // The staged batch decode with one erasure pattern PER STRIPE (k_mono_masks): the
 // patterns come from a device array of descriptors instead of the kernel arguments.
 // Descriptor of stripe b, at desc + b * desc_words (32-byte aligned, so a wave's

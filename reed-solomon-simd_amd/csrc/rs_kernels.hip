@@ -485,11 +485,19 @@ __device__ __forceinline__ void store_rows(const PassArgs &A, const Ctx &c, uint
         uint32_t l = lo[i], h = hi[i];
         if (A.work_out) {
             p = A.work_out + uint64_t(r) * A.work_stride;
-        } else if (r >= A.dst.row_begin && r < A.dst.row_end) {
-            p = const_cast<uint8_t *>(A.dst.base) + uint64_t(r - A.dst.row_begin) * A.dst.stride;
+        } else {
+            if (r >= A.dst.row_begin && r < A.dst.row_end) {
+                p = const_cast<uint8_t *>(A.dst.base) + uint64_t(r - A.dst.row_begin) * A.dst.stride;
+            } else if constexpr (REVEAL) {
+                // repair: the recovery rows' map (empty in a decode: a uniform test, never entered)
+                if (A.dst2.row_end != 0 && r >= A.dst2.row_begin && r < A.dst2.row_end)
+                    p = const_cast<uint8_t *>(A.dst2.base) + uint64_t(r - A.dst2.row_begin) * A.dst2.stride;
+            }
             if constexpr (REVEAL) {
-                if (rinfo[j] & 0x10000u) gf_mul4(l, h, tabV + j * 20u);
-                else p = nullptr;
+                if (p) {
+                    if (rinfo[j] & 0x10000u) gf_mul4(l, h, tabV + j * 20u);
+                    else p = nullptr;
+                }
             }
         }
         if (p && c.pk_ok) {

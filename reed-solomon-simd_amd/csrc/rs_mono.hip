@@ -724,14 +724,28 @@ __device__ __forceinline__ void run_seq(const TS &ts, Col<L, LR, E> &c, uint32_t
     }
 }
 
-// Decode: does this wave hold, after the FFT's remap, any row of A.dst?
+// The second destination of a repair (rs_device.hpp MonoArgs2; TWO): the map of
+// the recovery rows and this workgroup's stripe's base pointer.  The decode's
+// instantiations (TWO = false) never read it.
+struct Dst2 {
+    RowMap m;
+    uint8_t *base = nullptr;
+};
+[[maybe_unused]] __device__ __forceinline__ bool in_map(const RowMap &m, uint32_t r) {
+    return r - m.row_begin < m.row_end - m.row_begin;
+}
+
+// Decode: does this wave hold, after the FFT's remap, any row of A.dst (TWO: or of d2)?
 // (there the wave's rows are one block of 2^IW consecutive rows)
-template <int L, int LR, int SPLIT = 0>
-__device__ __forceinline__ bool wave_stores(const MonoCore &A, uint32_t wave, uint32_t base = 0) {
+template <int L, int LR, int SPLIT = 0, bool TWO = false>
+__device__ __forceinline__ bool wave_stores(const MonoCore &A, uint32_t wave, uint32_t base = 0,
+                                            const Dst2 &d2 = Dst2{}) {
     using S = SeqOf<L, LR, true, SPLIT>;
     constexpr int I = S::v.count;
     const uint32_t lo = lane_rows<S, I>(0, wave) + base, hi = lo + (1u << (LR + 6));
-    return lo < A.dst.row_end && hi > A.dst.row_begin;
+    bool any = lo < A.dst.row_end && hi > A.dst.row_begin;
+    if constexpr (TWO) any = any || (lo < d2.m.row_end && hi > d2.m.row_begin);
+    return any;
 }
 
 // Base pointers of this workgroup's stripe (wave-uniform, computed once).
@@ -983,21 +997,24 @@ template <int LR>
 struct RevealTabs {
     uint32_t t[1 << LR][16];
 };
-template <typename S, int I, int LR>
-__device__ __forceinline__ uint32_t reveal_log(const MonoCore &A, const uint32_t *rowinfo, uint32_t r) {
+template <typename S, int I, int LR, bool TWO = false>
+__device__ __forceinline__ uint32_t reveal_log(const MonoCore &A, const uint32_t *rowinfo, uint32_t r,
+                                               const Dst2 &d2 = Dst2{}) {
     const uint32_t f = rowinfo[r];
-    const bool need = (f & 0x10000u) && r >= A.dst.row_begin && r < A.dst.row_end;
+    bool need = (f & 0x10000u) && r >= A.dst.row_begin && r < A.dst.row_end;
+    if constexpr (TWO) need = need || ((f & 0x10000u) && in_map(d2.m, r));
     return need ? 65535u - (f & 0xFFFFu) : 0u;
 }
-template <int L, int LR, int SPLIT = 0>
+template <int L, int LR, int SPLIT = 0, bool TWO = false>
 __device__ __forceinline__ void reveal_issue(const MonoCore &A, const uint32_t *rowinfo, RevealTabs<LR> &rt,
-                                             uint32_t lane, uint32_t wave, uint32_t base = 0) {
+                                             uint32_t lane, uint32_t wave, uint32_t base = 0,
+                                             const Dst2 &d2 = Dst2{}) {
     using S = SeqOf<L, LR, true, SPLIT>;
     constexpr int I = S::v.count;
     const uint32_t a = lane_rows<S, I>(lane, wave) + base;
     static_for<0, (1 << LR)>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        quad_gather2(A.lut, reveal_log<S, I, LR>(A, rowinfo, a | reg_rows<S, I, LR>(i)), lane, rt.t[i]);
+        quad_gather2(A.lut, reveal_log<S, I, LR, TWO>(A, rowinfo, a | reg_rows<S, I, LR>(i), d2), lane, rt.t[i]);
     });
 }
 
@@ -1007,10 +1024,12 @@ __device__ __forceinline__ void reveal_issue(const MonoCore &A, const uint32_t *
 // from reveal_issue (2-element packs), else gathered here.
 // (AT_IFFT: rows in the placement at the end of the IFFT -- the half-split
 // kernels' work rows, kMonoHalfI)
-template <int L, int LR, bool REVEAL, int SPLIT = 0, int E = 4, bool AT_IFFT = false>
+// (TWO: a repair's second map d2 -- a row goes to the map that holds it)
+template <int L, int LR, bool REVEAL, int SPLIT = 0, int E = 4, bool AT_IFFT = false, bool TWO = false>
 __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *rowinfo, uint32_t chunk,
                                           const PackIO &io, const StripeBases &sb, Col<L, LR, E> &c, uint32_t lane,
-                                          uint32_t wave, const RevealTabs<LR> *rt = nullptr) {
+                                          uint32_t wave, const RevealTabs<LR> *rt = nullptr,
+                                          const Dst2 &d2 = Dst2{}) {
     using S = SeqOf<L, LR, !AT_IFFT, SPLIT>;
     constexpr uint32_t PC = Fmt<E>::kPC;
     constexpr int I = S::v.count;
@@ -1029,7 +1048,7 @@ __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *row
                 }
             }
             const uint32_t r = a | reg_rows<S, I, LR>(i);
-            const uint32_t lg = reveal_log<S, I, LR>(A, rowinfo, r);
+            const uint32_t lg = reveal_log<S, I, LR, TWO>(A, rowinfo, r, d2);
             uint32_t t[Fmt<E>::kTW];
             const uint4 *q = reinterpret_cast<const uint4 *>(A.lut) + lg * PC;
 #pragma unroll
@@ -1056,11 +1075,18 @@ __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *row
     const uint32_t off = io.lo + ((lane & 1u) ? io.hi_delta : 0u);
     const uint32_t r0 = paired_row<S, I, LR>(lane, wave, 0) + base;
     uint8_t *const p0 = const_cast<uint8_t *>(map_base(A.dst, sb.dst, r0));  // (see row_at)
+    uint8_t *q0 = nullptr;
+    if constexpr (TWO) q0 = const_cast<uint8_t *>(map_base(d2.m, d2.base, r0));
     static_for<0, 2 * R>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         constexpr uint32_t D = paired_delta<S, I, LR>(j);
         const uint32_t r = r0 + D;
-        if (r - A.dst.row_begin < A.dst.row_end - A.dst.row_begin) {
+        bool in = r - A.dst.row_begin < A.dst.row_end - A.dst.row_begin, in2 = false;
+        if constexpr (TWO) {
+            in2 = in_map(d2.m, r);
+            in = in || in2;
+        }
+        if (in) {
             bool keep = true;
             if constexpr (REVEAL) keep = rowinfo[r] & 0x10000u;
 #if defined(RS_MONO_SKIP_IO) || defined(RS_MONO_SKIP_STORES)
@@ -1068,6 +1094,8 @@ __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *row
 #endif
             if (keep) {
                 uint8_t *p = p0 + uint64_t(D) * A.dst.stride;
+                if constexpr (TWO)
+                    if (in2) p = q0 + uint64_t(D) * d2.m.stride;
                 if constexpr (E == 2) st_half(p + off, w[j], io);
 #ifndef RS_MONO_NO_NT_STORE  // streaming (non-temporal) row stores: profiles/r02g/ab_nt
                 else if (!io.bytes) __builtin_nontemporal_store(w[j], reinterpret_cast<uint32_t *>(p + off));
@@ -1759,8 +1787,11 @@ using MonoArgT = std::conditional_t<MODE == kMonoDecode && STAGED, MonoArgs, Mon
 template <int MODE, bool STAGED, bool MASKS>
 using MonoArgM = std::conditional_t<MASKS, MonoMaskArgs, MonoArgT<MODE, STAGED>>;
 
-template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, bool MASKS = false>
-__device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K) {
+// TWO (k_mono_repair): the decode with a second destination map (KA = MonoArgs2)
+template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, bool MASKS = false, bool TWO = false,
+          typename KA = MonoArgM<MODE, STAGED, MASKS>>
+__device__ __forceinline__ void mono_body(const KA &K) {
+    static_assert(!TWO || (!MASKS && (MODE == kMonoDecode || MODE == kMonoHalfFDec)), "second destination: decodes");
     static_assert(!MASKS || (MODE == kMonoDecode && STAGED && BATCH && !SPLIT),
                   "per-stripe patterns: the staged batch decode, plain plan");
     MonoCore A;  // the scalar arguments; the erasure bitmaps stay in K
@@ -1879,6 +1910,11 @@ __device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K
     // the pack's bytes in the caller's rows (tails: shards.rs:38-74)
     // (quad encode: 2-element column packs, computed as 4-element pair-row packs)
     const PackIO io = E == 4 && MODE != kMonoQuadEnc ? pack_io(A.fmt, pk) : pack_io2(A.fmt, pk);
+    Dst2 d2;
+    if constexpr (TWO) {
+        d2.m = K.dst2;
+        d2.base = const_cast<uint8_t *>(K.dst2.base) + (BATCH ? uint64_t(blockIdx.y) * K.dst2_bstride : 0);
+    }
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // half-split modes (kMonoHalf*): this workgroup's half; its transform uses one
@@ -2262,7 +2298,7 @@ __device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K
                     write3();
                     (void)alive;
                     if constexpr (kPreReveal)
-                        if (alive) reveal_issue<L, LR, PK>(A, ri, rt, lane, wave, HFD ? hh << L : 0u);
+                        if (alive) reveal_issue<L, LR, PK, TWO>(A, ri, rt, lane, wave, HFD ? hh << L : 0u, d2);
                 };
             };
             if constexpr (SPLIT) {
@@ -2279,7 +2315,7 @@ __device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K
                 using SF = SeqOf<L, LR, true, PK>;
                 constexpr int NLF = num_layers(SF::v);
                 const bool out = out_wave;
-                const bool alive = out && wave_stores<L, LR, PK>(A, wave);
+                const bool alive = out && wave_stores<L, LR, PK, TWO>(A, wave, 0, d2);
                 constexpr uint32_t kTopI = (G::n >> G::IW) - 2, kTopF = G::kShI + (G::n >> G::FLO) - 2;
                 split_top<L, LR>(c, plane, lds + G::words_dec, shared + kTopI * G::SW, shared + kTopF * G::SW, lane, wave,
                                  A.out_half, ii == 0, fi == 0);
@@ -2341,7 +2377,7 @@ __device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K
                 RS_MSTAMP(6);
                 using SF = SeqOf<L, LR, true, PK>;
                 constexpr int NLF = num_layers(SF::v);
-                const bool alive = !HFD || wave_stores<L, LR, PK>(A, wave, hh << L);
+                const bool alive = !HFD || wave_stores<L, LR, PK, TWO>(A, wave, hh << L, d2);
                 issue4(alive);
                 run_seq<L, LR, true, RS_MONO_LDS_PF, G::B0 ? NLF - 1 : -1, PK>(ts, c, plane, lane, wave, pre3(alive),
                                                                                 alive, true, write4, fi == 0);
@@ -2357,7 +2393,7 @@ __device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K
                 RS_MSTAMP(5);
                 using SF = SeqOf<L, LR, true, PK>;
                 constexpr int NLF = num_layers(SF::v);
-                const bool alive = !DEC || wave_stores<L, LR, PK>(A, wave);
+                const bool alive = !DEC || wave_stores<L, LR, PK, TWO>(A, wave, 0, d2);
                 issue4(alive);  // (waves that stop early all read one table: no branch around the loads)
                 if constexpr (DEC) formal_derivative<L, LR>(c, plane, lane, wave);
                 run_seq<L, LR, true, RS_MONO_LDS_PF, G::B0 ? NLF - 1 : -1, PK>(ts, c, plane, lane, wave, pre3(alive), alive,
@@ -2379,8 +2415,8 @@ __device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K
                 quad_layer0<L, LR, SQ, SQ::v.count, true>(c, qtab + QW * kQuad0Slot, lane, wave);  // FFT layer 0
                 store_quad<L, LR, PK>(A, io, sb, c, lane, wave);
             } else {
-                store_col<L, LR, DEC || HFD, PK>(A, ri, HALF_F ? hh : 0u, io, sb, c, lane, wave,
-                                                 kPreReveal && G::WB > 0 ? &rt : nullptr);
+                store_col<L, LR, DEC || HFD, PK, E, false, TWO>(A, ri, HALF_F ? hh : 0u, io, sb, c, lane, wave,
+                                                                kPreReveal && G::WB > 0 ? &rt : nullptr, d2);
             }
             RS_MSTAMP(11);
       };
@@ -2422,7 +2458,7 @@ __device__ __forceinline__ void mono_body(const MonoArgM<MODE, STAGED, MASKS> &K
         run_seq<L, LR, false, kMonoPrefetch>(GlobalTabs{img_i}, c, plane, lane, wave, NoHook{});
         formal_derivative<L, LR>(c, plane, lane, wave);
         run_seq<L, LR, true, kMonoPrefetch>(GlobalTabs{img_f}, c, plane, lane, wave, NoHook{});
-        store_col<L, LR, true>(A, A.rowinfo, 0, io, sb, c, lane, wave);
+        store_col<L, LR, true, 0, 4, false, TWO>(A, A.rowinfo, 0, io, sb, c, lane, wave, nullptr, d2);
     }
 }
 
@@ -2526,6 +2562,93 @@ hipError_t launch_m(int L, const MonoArgs &A, hipStream_t s) {
 }
 
 }  // namespace
+
+#ifdef RS_MONO_REPAIR_TU
+// rs_repair.hip: this file's kernel body compiled a second time, as a translation
+// unit of its own that holds only the repair instantiations (TWO: a second
+// destination map, rs_device.hpp MonoArgs2).  The decode's kernels are not part of
+// it and this file's own object holds none of these: the two compile side by side.
+namespace {
+
+template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E>
+__global__ void __launch_bounds__(1 << (L - LR)) k_mono_repair(const MonoArgs2 A) {
+    mono_body<L, LR, MODE, STAGED, BATCH, SPLIT, E, false, true>(A);
+}
+
+// grid_y: stripes (BATCH) or halves (kMonoHalfFDec)
+template <int L, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E>
+hipError_t launch_repair_ls(const MonoArgs2 &A, uint32_t grid_y, hipStream_t s) {
+    constexpr int LR = mono_lr(L, STAGED);
+    using G = Stage<L, LR, mono_pk(MODE, STAGED, SPLIT), E>;
+    size_t lds = STAGED ? size_t(SPLIT ? G::words_split : MODE == kMonoDecode ? G::words_dec : G::words_enc) * 4
+                        : size_t(8) << L;
+    if (E == 2 && lds <= 80 * 1024) lds = 84 * 1024;  // (as launch_ls)
+    static std::atomic<uint64_t> attr_devs{0};
+    if (lds > 65536) {
+        hipError_t e = lds_attr_once(
+            attr_devs, reinterpret_cast<const void *>(&k_mono_repair<L, LR, MODE, STAGED, BATCH, SPLIT, E>), int(lds));
+        if (e != hipSuccess) return e;
+    }
+    k_mono_repair<L, LR, MODE, STAGED, BATCH, SPLIT, E>
+        <<<dim3(8u * A.packs_per_xcd, grid_y), 1 << (L - LR), lds, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono_repair<%d, %d, %d, %s, %s, %s, %d>", L, LR, MODE,
+             STAGED ? "true" : "false", BATCH ? "true" : "false", SPLIT ? "true" : "false", E);
+    return hipGetLastError();
+}
+
+// the staged fused-eval_poly repair of 2^L work rows: always the batch form (one
+// stripe: grid.y = 1), so each (L, plan, format) is built once
+template <int L>
+hipError_t launch_repair_staged(const MonoArgs2 &A, hipStream_t s) {
+    if constexpr (!(RS_MONO_HAS_L(L) && RS_MONO_HAS_MODE(kMonoDecode) && staged_l(L))) {
+        return hipErrorNotSupported;
+    } else {
+        if (!A.fused_eval || A.chunks != 1 || A.stripes == 0 || (A.elems != 2 && A.elems != 4))
+            return hipErrorInvalidValue;
+        if constexpr (split_l(L)) {
+            if (A.split)
+                return A.elems == 2 ? launch_repair_ls<L, kMonoDecode, true, true, true, 2>(A, A.stripes, s)
+                                    : launch_repair_ls<L, kMonoDecode, true, true, true, 4>(A, A.stripes, s);
+        }
+        if (A.split) return hipErrorInvalidValue;
+        return A.elems == 2 ? launch_repair_ls<L, kMonoDecode, true, true, false, 2>(A, A.stripes, s)
+                            : launch_repair_ls<L, kMonoDecode, true, true, false, 4>(A, A.stripes, s);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_mono_repair(int L, const MonoArgs2 &A, hipStream_t s) {
+    if (A.packs == 0) return hipSuccess;
+    switch (L) {
+        case 7: return launch_repair_staged<7>(A, s);
+        case 8: return launch_repair_staged<8>(A, s);
+        case 9: return launch_repair_staged<9>(A, s);
+        case 10: return launch_repair_staged<10>(A, s);
+        case 11: return launch_repair_staged<11>(A, s);
+        case 12:  // the unstaged kernel: rowinfo from k_eval_poly, one stripe, 4-element packs
+            if constexpr (RS_MONO_HAS_L(12) && RS_MONO_HAS_MODE(kMonoDecode) && !staged_l(12)) {
+                if (A.fused_eval || A.stripes != 1 || A.elems != 4 || A.chunks != 1 || A.split)
+                    return hipErrorInvalidValue;
+                return launch_repair_ls<12, kMonoDecode, false, false, false, 4>(A, 1, s);
+            }
+            return hipErrorNotSupported;
+        default: return hipErrorNotSupported;
+    }
+}
+
+hipError_t launch_mono_half_repair(uint32_t halves, const MonoArgs2 &A, hipStream_t s) {
+    if (A.packs == 0 || halves == 0) return hipSuccess;
+    if (halves > 2 || A.stripes != 1 || A.chunks != 1) return hipErrorInvalidValue;
+    if constexpr (!(RS_MONO_HAS_L(11) && staged_l(11))) {
+        return hipErrorNotSupported;
+    } else {
+        return A.elems == 2 ? launch_repair_ls<11, kMonoHalfFDec, true, false, false, 2>(A, halves, s)
+                            : launch_repair_ls<11, kMonoHalfFDec, true, false, false, 4>(A, halves, s);
+    }
+}
+
+#else  // !RS_MONO_REPAIR_TU
 
 hipError_t launch_mono_half(int mode, uint32_t halves, const MonoArgs &A, hipStream_t s) {
     if (A.packs == 0 || halves == 0) return hipSuccess;
@@ -2663,5 +2786,7 @@ hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t s) {
         default: return hipErrorNotSupported;
     }
 }
+
+#endif  // RS_MONO_REPAIR_TU
 
 }  // namespace rs

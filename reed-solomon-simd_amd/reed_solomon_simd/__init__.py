@@ -103,6 +103,12 @@ _sig("rs_decode_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u6
      _u64, ctypes.c_char_p, _vp, _u64, _u64, _vp, _E)
 _sig("rs_decode_device_batch_masks", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _u64, _u64,
      _vp, _vp, _u64, _u64, ctypes.POINTER(ctypes.c_uint8), _vp, _E)
+_sig("rs_repair_device", _int, _vp, _int, _u64, _u64, _u64, _vp, ctypes.c_char_p, _vp, ctypes.c_char_p, _vp, _vp, _vp,
+     _E)
+_sig("rs_repair_device_strided", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, ctypes.c_char_p, _vp, _u64,
+     ctypes.c_char_p, _vp, _u64, _vp, _u64, _vp, _E)
+_sig("rs_repair_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, ctypes.c_char_p, _vp, _u64,
+     _u64, ctypes.c_char_p, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _E)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -879,6 +885,57 @@ def decode_device(original_count: int, recovery_count: int, shard_bytes: int, d_
                                          _ptr(d_original), _row_stride(d_original), op, _ptr(d_recovery),
                                          _row_stride(d_recovery), rp, _ptr(d_restored), _row_stride(d_restored),
                                          _stream(stream), ctypes.byref(err)), err)
+
+
+def repair_device(original_count: int, recovery_count: int, shard_bytes: int, d_original, original_present,
+                  d_recovery, recovery_present, d_restored, d_recovery_out, stream=None, rate_: int = RATE_DEFAULT,
+                  ctx: Optional[Context] = None) -> None:
+    """decode_device that also rebuilds the missing RECOVERY shards (rs_repair_device_strided):
+    missing originals go to d_restored, missing recovery shard i to row i of d_recovery_out
+    [recovery_count, shard_bytes]; present rows of either are not written.  d_recovery_out may be
+    d_recovery and d_restored may be d_original (in place: the holes are filled).  Runs when only
+    recovery shards are missing; with nothing missing it does nothing."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    op = _check_mask(present_mask(original_present), original_count, "original_present")
+    rp = _check_mask(present_mask(recovery_present), recovery_count, "recovery_present")
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    _check_matrix(d_restored, original_count, shard_bytes, "d_restored")
+    _check_matrix(d_recovery_out, recovery_count, shard_bytes, "d_recovery_out")
+    err = _RsError()
+    _raise(_lib.rs_repair_device_strided(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
+                                         _ptr(d_original), _row_stride(d_original), op, _ptr(d_recovery),
+                                         _row_stride(d_recovery), rp, _ptr(d_restored), _row_stride(d_restored),
+                                         _ptr(d_recovery_out), _row_stride(d_recovery_out), _stream(stream),
+                                         ctypes.byref(err)), err)
+
+
+def repair_device_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, original_present,
+                        d_recovery, recovery_present, d_restored, d_recovery_out, stream=None,
+                        rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None) -> None:
+    """repair_device on a batch of stripes sharing ONE erasure pattern (rs_repair_device_batch);
+    tensors [stripes, rows, shard_bytes] as for decode_device_batch."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    _check_matrix(d_restored, original_count, shard_bytes, "d_restored", 3)
+    _check_matrix(d_recovery_out, recovery_count, shard_bytes, "d_recovery_out", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n or d_restored.shape[0] != n or d_recovery_out.shape[0] != n:
+        raise ValueError("batches differ in stripe count")
+    (o_row, o_b), (r_row, r_b), (x_row, x_b), (y_row, y_b) = (
+        _batch_strides(d_original), _batch_strides(d_recovery), _batch_strides(d_restored),
+        _batch_strides(d_recovery_out))
+    err = _RsError()
+    _raise(_lib.rs_repair_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                       d_original.data_ptr(), o_row, o_b,
+                                       _check_mask(present_mask(original_present), original_count, "original_present"),
+                                       d_recovery.data_ptr(), r_row, r_b,
+                                       _check_mask(present_mask(recovery_present), recovery_count, "recovery_present"),
+                                       d_restored.data_ptr(), x_row, x_b, d_recovery_out.data_ptr(), y_row, y_b,
+                                       _stream(stream), ctypes.byref(err)), err)
 
 
 class DeviceCall:
