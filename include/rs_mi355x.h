@@ -32,6 +32,8 @@
  *   rs_encode_device / rs_decode_device (+ _strided, + _batch: many
  *   stripes of one shape in one launch; rs_decode_device_batch_masks: the
  *   batch decode with an erasure pattern per stripe)
+ *   rs_repair_device (+ _strided, + _batch; rs_repair_device_batch_masks: a
+ *   pattern per stripe): the decode that also rebuilds missing recovery shards
  *
  * Thread-safety: a context may be shared by threads (like DefaultEngine:
  * Send + Sync, src/lib.rs:385-409): calls on one context are serialized on the
@@ -316,9 +318,9 @@ rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t o
  * Asynchronous on `stream`; scratch per (context, stream); profile records as
  * the decode's, the bytes of a launch counting the recovery rows it writes.
  *   Not covered yet (each can follow now that the kernels take a second
- * destination): per-stripe patterns (rs_decode_device_batch_masks), the
- * host-memory pipeline (rs_decode_host), the rs_decoder object API and the
- * sharded multi-device decoder. */
+ * destination): the host-memory pipeline (rs_decode_host), the rs_decoder
+ * object API and the sharded multi-device decoder.  Per-stripe patterns:
+ * rs_repair_device_batch_masks, below. */
 rs_status rs_repair_device(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
                            uint64_t shard_bytes, const void *d_original, const uint8_t *original_present,
                            const void *d_recovery, const uint8_t *recovery_present, void *d_restored,
@@ -336,6 +338,52 @@ rs_status rs_repair_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  uint64_t restored_stride, uint64_t restored_stripe_stride, void *d_recovery_out,
                                  uint64_t recovery_out_stride, uint64_t recovery_out_stripe_stride, void *stream,
                                  rs_error *err);
+/* The batch repair with one pattern PER STRIPE (a scrub or rebuild pass over
+ * many objects, each of which lost a different mix of original and recovery
+ * shards; every hole filled in place).  Matrices, strides and alignment rules are
+ * those of rs_repair_device_batch; the masks are HOST arrays of stripes x
+ * original_count / stripes x recovery_count bytes, stripe-major, as in
+ * rs_decode_device_batch_masks.
+ *   Result: stripe b ends up exactly as if rs_repair_device_strided had been
+ * called on it with row b of the two masks: only missing rows of either output
+ * are written, absent input rows are never read, and a stripe that misses
+ * nothing does no work.  In place (d_recovery_out == d_recovery, d_restored ==
+ * d_original, equal strides) is allowed as above.  Unaligned bases or strides
+ * take the byte-wise path.
+ *   Errors, all before any device work: null context / pointers (d_recovery_out
+ * included) -> RS_ERR_INVALID_ARGUMENT, then rs_validate, then the four row
+ * strides; stripes == 0 -> RS_OK.  Then every stripe's pattern is checked on the
+ * host in stripe order.  stripe_status as in rs_decode_device_batch_masks: NULL =
+ * all or nothing (the first undecodable stripe's NotEnoughShards counts, its
+ * number in err->index, nothing launched or written); non-NULL = one rs_status
+ * per stripe, undecodable stripes skipped and flagged, the rest repaired, RS_OK.
+ * A batch in which no stripe misses anything returns RS_OK, launches nothing and
+ * does not touch the context.
+ *   Where rs_repair_device_batch runs a batch as one launch (up to 2^11 work
+ * rows on the column kernel) so does this call: one launch of
+ * k_mono_repair_masks per 65535 stripes, the patterns as per-stripe descriptors
+ * copied on `stream` ahead of it.  That launch also takes the stripes that miss
+ * recovery shards only through the decode's kernels: a lone rs_repair_device
+ * call sends a single run of them to the narrowed encode (7.5 vs 15.3 us at
+ * 1024:1024 x 1 KiB), but a batch is heterogeneous and a second launch costs
+ * more than it saves.  Elsewhere the stripes run one after another, each by
+ * the route rs_repair_device_strided takes for its pattern (the narrowed encode
+ * included).
+ *   Measured (tools/repair_masks_time.py, profiles/repair_masks/): 64 stripes of
+ * 1024:1024 x 1 KiB, each with its own random 1 % of the 2048 shards lost:
+ * 64 rs_repair_device calls 1083 us, this call 618 us (0.57), rs_repair_device_batch
+ * with one shared pattern 556 us (1.11), rs_decode_device_batch_masks on the same
+ * masks, originals only, 580 us (1.07). */
+rs_status rs_repair_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                       uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                       const void *d_original, uint64_t original_stride,
+                                       uint64_t original_stripe_stride, const uint8_t *original_present,
+                                       const void *d_recovery, uint64_t recovery_stride,
+                                       uint64_t recovery_stripe_stride, const uint8_t *recovery_present,
+                                       void *d_restored, uint64_t restored_stride, uint64_t restored_stripe_stride,
+                                       void *d_recovery_out, uint64_t recovery_out_stride,
+                                       uint64_t recovery_out_stripe_stride, uint8_t *stripe_status, void *stream,
+                                       rs_error *err);
 
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x

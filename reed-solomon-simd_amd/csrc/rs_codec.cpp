@@ -1557,6 +1557,39 @@ void decode_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64
     }
 }
 
+// Repair of g.stripes stripes that share one pattern with something missing
+// (rs_repair_device_batch; one stripe of rs_repair_device_batch_masks off the
+// fused route): the route that pattern takes.
+// Every original present and the missing recovery rows one run [lo, hi): the
+// encode with its destination narrowed to that run -- every encode kernel stores
+// only the rows of its destination map -- is about twice as fast as the decode's
+// kernels (1024:1024 x 1 KiB, one shard: 8.3 vs 15.3 us; 64 stripes 223 vs 493 us,
+// profiles/repair/repair_time_decode_route.txt).  Each further run would cost one
+// more encode, which is the decode route's time for ANY pattern: those, and
+// every repair with an original missing, take the decode's kernels.
+void repair_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64_t N, uint64_t M,
+                const uint8_t *orig, const uint8_t *orig_present, const uint8_t *rec, const uint8_t *rec_present,
+                uint8_t *restored, uint8_t *rec_out, hipStream_t s) {
+    uint64_t have_o = 0;
+    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
+    uint32_t lo = 0, hi = 0, runs = 0;
+    if (have_o == N)
+        for (uint32_t i = 0; i < M; ++i)
+            if (!rec_present[i]) {
+                if (runs == 0 || i != hi) ++runs, lo = runs == 1 ? i : lo;
+                hi = i + 1;
+            }
+    if (have_o == N && runs == 1) {
+        Geom ge = g;  // the encode's recovery matrix is rec_out
+        ge.rec_stride = g.out2_stride;
+        ge.rec_bstride = g.out2_bstride;
+        if (high) encode_high(ctx, ws, ge, N, M, orig, rec_out, s, lo, hi);
+        else encode_low(ctx, ws, ge, N, M, orig, rec_out, s, lo, hi);
+        return;
+    }
+    decode_dev(ctx, ws, high, g, N, M, orig, orig_present, rec, rec_present, restored, s, rec_out);
+}
+
 // Presence bytes p[0 .. n) (non-zero = present) as bits [bit0, bit0 + n) of the
 // words w (clear there on entry; little-endian host); returns how many are set.
 // Eight bytes at a time where bit0 is byte aligned: the high bit of every
@@ -1590,21 +1623,39 @@ uint32_t put_present(const uint8_t *p, uint32_t n, uint32_t bit0, uint32_t *w) {
 // destination map (the narrowed map and the split plan are decisions about ONE
 // pattern; the reveal writes erased rows only either way).  Elsewhere the
 // stripes decode one after another, as decode_dev's batches do.
+//
+// Repair (rec_out != nullptr; rs_repair_device_batch_masks): the same descriptors
+// -- a stripe's erased bits are span & ~received, and span covers the recovery
+// rows' work rows -- and one launch of k_mono_repair_masks with the second
+// destination map over rec_out, both maps whole.  HighRate's padding rows
+// [M, chunk) are erased too and lie in neither map: never written.  The caller
+// skips only stripes that miss nothing at all (or cannot be decoded); a stripe
+// that misses recovery rows alone runs here with the rest -- alone it would take
+// the narrowed encode (repair_dev; 7.5 vs 15.3 us), but a batch is heterogeneous
+// and a second launch for such stripes costs more than it saves.  Elsewhere every
+// stripe takes the route its own pattern would take alone (repair_dev).
 void decode_masks_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64_t N, uint64_t M,
                       const uint8_t *orig, const uint8_t *orig_present, const uint8_t *rec,
-                      const uint8_t *rec_present, uint8_t *restored, const uint8_t *skip, hipStream_t s) {
+                      const uint8_t *rec_present, uint8_t *restored, const uint8_t *skip, hipStream_t s,
+                      uint8_t *rec_out = nullptr) {
     const DecodeRows dr = decode_rows(ctx, high, g, N, M);
     const uint32_t chunk = dr.chunk, end = dr.end, nd = dr.nd, u = dr.u;
     if (!(use_mono(ctx, u, g, 1) && rs::mono_staged(int(u), 1) && nd <= rs::kMonoFusedRows)) {
         Geom g1 = g;
         g1.stripes = 1;
-        for (uint32_t b = 0; b < g.stripes; ++b)
-            if (!skip[b])
+        for (uint32_t b = 0; b < g.stripes; ++b) {
+            if (skip[b]) continue;
+            if (rec_out)
+                repair_dev(ctx, ws, high, g1, N, M, orig + b * g.orig_bstride, orig_present + b * N,
+                           rec + b * g.rec_bstride, rec_present + b * M, restored + b * g.out_bstride,
+                           rec_out + b * g.out2_bstride, s);
+            else
                 decode_dev(ctx, ws, high, g1, N, M, orig + b * g.orig_bstride, orig_present + b * N,
                            rec + b * g.rec_bstride, rec_present + b * M, restored + b * g.out_bstride, s);
+        }
         return;
     }
-    rs::MonoMaskArgs Mo;
+    rs::MonoMaskArgs2 Mo;
     static_cast<rs::MonoCore &>(Mo) = mono_args(ctx, u, g, true, true);
     Mo.src[0] = rs::RowMap{rec, g.rec(), high ? 0u : chunk, high ? uint32_t(M) : end};
     Mo.src_bstride[0] = g.rec_bstride;
@@ -1613,6 +1664,10 @@ void decode_masks_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, 
     Mo.nsrc = 2;
     Mo.dst = rs::RowMap{restored, g.out(), Mo.src[1].row_begin, Mo.src[1].row_end};
     Mo.dst_bstride = g.out_bstride;
+    if (rec_out) {
+        Mo.dst2 = rs::RowMap{rec_out, g.out2(), Mo.src[0].row_begin, Mo.src[0].row_end};
+        Mo.dst2_bstride = g.out2_bstride;
+    }
     Mo.fused_eval = 1;
     Mo.low_rate = high ? 0 : 1;
     Mo.end = end;
@@ -1634,8 +1689,10 @@ void decode_masks_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, 
         std::memset(d, 0, size_t(dw) * 4);
         if ((d[0] = skip[b] ? 1u : 0u)) continue;
         uint32_t rcv[rs::kMonoFusedRows / 32] = {};
-        // (received rows + missing originals = received recovery rows + N)
-        rows += put_present(rec_present + uint64_t(b) * M, uint32_t(M), high ? 0u : chunk, rcv) + N;
+        // (received rows + missing originals = received recovery rows + N;
+        // repair: + the missing recovery rows = N + M)
+        const uint32_t have_r = put_present(rec_present + uint64_t(b) * M, uint32_t(M), high ? 0u : chunk, rcv);
+        rows += (rec_out ? M : have_r) + N;
         put_present(orig_present + uint64_t(b) * N, uint32_t(N), high ? chunk : 0u, rcv);
         for (uint32_t k = 0; k < nw; ++k) {
             uint32_t *wv = d + rs::kMaskDescHead + 8u * (k / 4) + k % 4;
@@ -1650,8 +1707,18 @@ void decode_masks_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, 
     Mo.desc_words = dw;
     hipEvent_t ev = nullptr;
     if (t_prof_ctx) prof_begin(s, &ev);
-    check(rs::launch_mono_masks(int(u), Mo, s));
+    if (rec_out) check(rs::launch_mono_repair_masks(int(u), Mo, s));
+    else check(rs::launch_mono_masks(int(u), static_cast<const rs::MonoMaskArgs &>(Mo), s));
     if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), rows * uint64_t(g.packs) * 8);
+}
+
+// Repair of such a batch (rs_repair_device_batch_masks): skip[b] != 0 only for a
+// stripe that misses nothing at all, or cannot be decoded.
+void repair_masks_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, uint64_t N, uint64_t M,
+                      const uint8_t *orig, const uint8_t *orig_present, const uint8_t *rec,
+                      const uint8_t *rec_present, uint8_t *restored, uint8_t *rec_out, const uint8_t *skip,
+                      hipStream_t s) {
+    decode_masks_dev(ctx, ws, high, g, N, M, orig, orig_present, rec, rec_present, restored, skip, s, rec_out);
 }
 
 const char *hip_msg(hipError_t e) { return hipGetErrorString(e); }
@@ -2365,36 +2432,14 @@ rs_status rs_repair_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
         if (stripes > 1 && (g.orig_bstride | g.rec_bstride | g.out_bstride | g.out2_bstride) % 4)
             g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
         StreamWs sw(ctx, static_cast<hipStream_t>(stream));
-        // Every original present and the missing recovery rows one run [lo, hi): the
-        // encode with its destination narrowed to that run -- every encode kernel stores
-        // only the rows of its destination map -- is about twice as fast as the decode's
-        // kernels (1024:1024 x 1 KiB, one shard: 8.3 vs 15.3 us; 64 stripes 223 vs 493 us,
-        // profiles/repair/repair_time_decode_route.txt).  Each further run would cost one
-        // more encode, which is the decode route's time for ANY pattern: those, and
-        // every repair with an original missing, take the decode's kernels.
-        uint32_t lo = 0, hi = 0, runs = 0;
-        if (have_o == N)
-            for (uint32_t i = 0; i < M; ++i)
-                if (!rec_present[i]) {
-                    if (runs == 0 || i != hi) ++runs, lo = runs == 1 ? i : lo;
-                    hi = i + 1;
-                }
-        const bool by_encode = have_o == N && runs == 1;
-        Geom ge = g;  // the encode's recovery matrix is d_recovery_out
-        ge.rec_stride = g.out2_stride;
-        ge.rec_bstride = g.out2_bstride;
+        // (the route of the pattern -- narrowed encode or the decode's kernels: repair_dev)
         for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
-            g.stripes = ge.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
-            const uint8_t *o = static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride;
-            uint8_t *y = static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride;
-            if (by_encode) {
-                if (high) encode_high(ctx, sw.w, ge, N, M, o, y, static_cast<hipStream_t>(stream), lo, hi);
-                else encode_low(ctx, sw.w, ge, N, M, o, y, static_cast<hipStream_t>(stream), lo, hi);
-                continue;
-            }
-            decode_dev(ctx, sw.w, high, g, N, M, o, orig_present,
-                       static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride, rec_present,
-                       static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride, static_cast<hipStream_t>(stream), y);
+            g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
+            repair_dev(ctx, sw.w, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
+                       orig_present, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride, rec_present,
+                       static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
+                       static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride,
+                       static_cast<hipStream_t>(stream));
         }
         return set_err(err, RS_OK);
     });
@@ -2475,6 +2520,76 @@ rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
                              orig_present + b0 * N, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride,
                              rec_present + b0 * M, static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
                              skip.data() + b0, static_cast<hipStream_t>(stream));
+        }
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_repair_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                       uint64_t stripes, const void *d_orig, uint64_t orig_stride,
+                                       uint64_t orig_stripe_stride, const uint8_t *orig_present, const void *d_rec,
+                                       uint64_t rec_stride, uint64_t rec_stripe_stride, const uint8_t *rec_present,
+                                       void *d_restored, uint64_t restored_stride, uint64_t restored_stripe_stride,
+                                       void *d_recovery_out, uint64_t recovery_out_stride,
+                                       uint64_t recovery_out_stripe_stride, uint8_t *stripe_status, void *stream,
+                                       rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_restored) || !ptr_ok(d_recovery_out) ||
+        !orig_present || !rec_present)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S) ||
+        !stride_ok(recovery_out_stride, S))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        // every stripe's pattern, in stripe order, before any device work.
+        // skip: 1 = nothing missing (of either kind), 2 = not decodable (status mode)
+        std::vector<uint8_t> skip(stripes, 0);
+        bool work = false;
+        for (uint64_t b = 0; b < stripes; ++b) {
+            const uint8_t *op = orig_present + b * N, *rp = rec_present + b * M;
+            uint64_t have_o = 0, have_r = 0;
+            for (uint64_t i = 0; i < N; ++i) have_o += op[i] != 0;
+            for (uint64_t i = 0; i < M; ++i) have_r += rp[i] != 0;
+            if (stripe_status) stripe_status[b] = RS_OK;
+            if (have_o + have_r < N) {
+                if (stripe_status) {
+                    stripe_status[b] = RS_ERR_NOT_ENOUGH_SHARDS;
+                    skip[b] = 2;
+                    continue;
+                }
+                set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
+                if (err) {
+                    err->original_count = N, err->original_received_count = have_o;
+                    err->recovery_received_count = have_r;
+                    err->index = b;  // the stripe, as rs_decode_device_batch_masks
+                }
+                return RS_ERR_NOT_ENOUGH_SHARDS;
+            }
+            if (have_o == N && have_r == M) skip[b] = 1;
+            else work = true;
+        }
+        if (!work) return set_err(err, RS_OK);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored, d_recovery_out},
+                             recovery_out_stride);
+        g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
+        g.out2_bstride = recovery_out_stripe_stride ? recovery_out_stripe_stride : M * g.out2();
+        if ((g.orig_bstride | g.rec_bstride | g.out_bstride | g.out2_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
+        for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
+            g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
+            repair_masks_dev(ctx, sw.w, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
+                             orig_present + b0 * N, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride,
+                             rec_present + b0 * M, static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
+                             static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride, skip.data() + b0,
+                             static_cast<hipStream_t>(stream));
         }
         return set_err(err, RS_OK);
     });

@@ -324,6 +324,14 @@ struct MonoMaskArgs : MonoCore {
 };
 // Plain plan, fused eval_poly, grid.y = A.stripes (>= 1); 7 <= L <= 11, elems 2 or 4.
 hipError_t launch_mono_masks(int L, const MonoMaskArgs &A, hipStream_t stream);
+// The repair of such a batch (k_mono_repair_masks, built in rs_repair.hip): the
+// same descriptors (a stripe's erased bits cover the recovery rows' work rows too)
+// and the second destination map of MonoArgs2, both maps whole.
+struct MonoMaskArgs2 : MonoMaskArgs {
+    RowMap dst2;
+    uint64_t dst2_bstride = 0;
+};
+hipError_t launch_mono_repair_masks(int L, const MonoMaskArgs2 &A, hipStream_t stream);
 // Multi-chunk encodes of 2^L rows, 2 <= L <= 7 (rs_chunks.hip): HighRate (high:
 // A.chunks input chunks, images ifft_img + c * ifft_img_step, fft_img) or
 // LowRate (A.chunks output chunks, images ifft_img, fft_img + c * fft_img_step);

@@ -1787,11 +1787,13 @@ using MonoArgT = std::conditional_t<MODE == kMonoDecode && STAGED, MonoArgs, Mon
 template <int MODE, bool STAGED, bool MASKS>
 using MonoArgM = std::conditional_t<MASKS, MonoMaskArgs, MonoArgT<MODE, STAGED>>;
 
-// TWO (k_mono_repair): the decode with a second destination map (KA = MonoArgs2)
+// TWO (k_mono_repair): the decode with a second destination map (KA = MonoArgs2;
+// with MASKS, k_mono_repair_masks: KA = MonoMaskArgs2)
 template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, bool MASKS = false, bool TWO = false,
           typename KA = MonoArgM<MODE, STAGED, MASKS>>
 __device__ __forceinline__ void mono_body(const KA &K) {
-    static_assert(!TWO || (!MASKS && (MODE == kMonoDecode || MODE == kMonoHalfFDec)), "second destination: decodes");
+    // (MASKS and TWO together, k_mono_repair_masks: MASKS' own conditions below hold)
+    static_assert(!TWO || MODE == kMonoDecode || (!MASKS && MODE == kMonoHalfFDec), "second destination: decodes");
     static_assert(!MASKS || (MODE == kMonoDecode && STAGED && BATCH && !SPLIT),
                   "per-stripe patterns: the staged batch decode, plain plan");
     MonoCore A;  // the scalar arguments; the erasure bitmaps stay in K
@@ -2645,6 +2647,59 @@ hipError_t launch_mono_half_repair(uint32_t halves, const MonoArgs2 &A, hipStrea
     } else {
         return A.elems == 2 ? launch_repair_ls<11, kMonoHalfFDec, true, false, false, 2>(A, halves, s)
                             : launch_repair_ls<11, kMonoHalfFDec, true, false, false, 4>(A, halves, s);
+    }
+}
+
+namespace {
+
+// The staged batch repair with per-stripe patterns: k_mono_masks (below) with the
+// second destination map; the plain plan, both maps whole, bitmaps and the skip
+// word from the stripe's descriptor.
+template <int L, int E>
+__global__ void __launch_bounds__(1 << (L - 1)) k_mono_repair_masks(const MonoMaskArgs2 A) {
+    mono_body<L, 1, kMonoDecode, true, true, false, E, true, true>(A);
+}
+
+template <int L, int E>
+hipError_t launch_repair_masks_le(const MonoMaskArgs2 &A, hipStream_t s) {
+    constexpr int LR = mono_lr(L, true);
+    static_assert(LR == 1, "k_mono_repair_masks: 2 rows per lane");
+    using G = Stage<L, LR, mono_pk(kMonoDecode, true, false), E>;
+    size_t lds = size_t(G::words_dec) * 4;
+    if (E == 2 && lds <= 80 * 1024) lds = 84 * 1024;  // (as launch_ls)
+    static std::atomic<uint64_t> attr_devs{0};
+    if (lds > 65536) {
+        hipError_t e = lds_attr_once(attr_devs, reinterpret_cast<const void *>(&k_mono_repair_masks<L, E>), int(lds));
+        if (e != hipSuccess) return e;
+    }
+    k_mono_repair_masks<L, E><<<dim3(8u * A.packs_per_xcd, A.stripes), 1 << (L - LR), lds, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono_repair_masks<%d, %d>", L, E);
+    return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_repair_masks_l(const MonoMaskArgs2 &A, hipStream_t s) {
+    if constexpr (!(RS_MONO_HAS_L(L) && RS_MONO_HAS_MODE(kMonoDecode) && staged_l(L))) {
+        return hipErrorNotSupported;
+    } else {
+        return A.elems == 2 ? launch_repair_masks_le<L, 2>(A, s) : launch_repair_masks_le<L, 4>(A, s);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_mono_repair_masks(int L, const MonoMaskArgs2 &A, hipStream_t s) {
+    if (A.packs == 0 || A.stripes == 0) return hipSuccess;
+    if (!A.desc || A.desc_words != mask_desc_words(uint32_t(L)) || A.chunks != 1 || !A.fused_eval || A.split ||
+        (A.elems != 2 && A.elems != 4))
+        return hipErrorInvalidValue;
+    switch (L) {
+        case 7: return launch_repair_masks_l<7>(A, s);
+        case 8: return launch_repair_masks_l<8>(A, s);
+        case 9: return launch_repair_masks_l<9>(A, s);
+        case 10: return launch_repair_masks_l<10>(A, s);
+        case 11: return launch_repair_masks_l<11>(A, s);
+        default: return hipErrorNotSupported;
     }
 }
 

@@ -109,6 +109,8 @@ _sig("rs_repair_device_strided", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, c
      ctypes.c_char_p, _vp, _u64, _vp, _u64, _vp, _E)
 _sig("rs_repair_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, ctypes.c_char_p, _vp, _u64,
      _u64, ctypes.c_char_p, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _E)
+_sig("rs_repair_device_batch_masks", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _u64, _u64,
+     _vp, _vp, _u64, _u64, _vp, _u64, _u64, ctypes.POINTER(ctypes.c_uint8), _vp, _E)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -936,6 +938,53 @@ def repair_device_batch(original_count: int, recovery_count: int, shard_bytes: i
                                        _check_mask(present_mask(recovery_present), recovery_count, "recovery_present"),
                                        d_restored.data_ptr(), x_row, x_b, d_recovery_out.data_ptr(), y_row, y_b,
                                        _stream(stream), ctypes.byref(err)), err)
+
+
+def repair_device_batch_masks(original_count: int, recovery_count: int, shard_bytes: int, d_original,
+                              original_present, d_recovery, recovery_present, d_restored, d_recovery_out, *,
+                              status: bool = False, stream=None, ctx: Optional[Context] = None,
+                              rate_: int = RATE_DEFAULT):
+    """repair_device on a batch of stripes, each with its OWN pattern (rs_repair_device_batch_masks);
+    tensors [stripes, rows, shard_bytes] as for repair_device_batch, masks [stripes, count] arrays of
+    0/1 as for decode_device_batch_masks.  Stripe b ends up as repair_device would leave it with
+    row b of the masks; a stripe that misses nothing is not touched.  In place (d_restored is
+    d_original, d_recovery_out is d_recovery) is allowed.
+
+    status=False: a stripe with fewer than original_count shards raises NotEnoughShards with that
+    stripe's counts and its number in the attribute `stripe`; nothing has been written then.
+    status=True: returns a numpy uint8 array of one rs_status code per stripe (0 = ok, 7 = not
+    enough shards: that stripe is left alone, the others are repaired) and does not raise for them."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    _check_matrix(d_restored, original_count, shard_bytes, "d_restored", 3)
+    _check_matrix(d_recovery_out, recovery_count, shard_bytes, "d_recovery_out", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n or d_restored.shape[0] != n or d_recovery_out.shape[0] != n:
+        raise ValueError("batches differ in stripe count")
+    op = _stripe_masks(original_present, n, original_count, "original_present")
+    rp = _stripe_masks(recovery_present, n, recovery_count, "recovery_present")
+    (o_row, o_b), (r_row, r_b), (x_row, x_b), (y_row, y_b) = (
+        _batch_strides(d_original), _batch_strides(d_recovery), _batch_strides(d_restored),
+        _batch_strides(d_recovery_out))
+    codes = (ctypes.c_uint8 * n)() if status else None
+    err = _RsError()
+    code = _lib.rs_repair_device_batch_masks(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                             d_original.data_ptr(), o_row, o_b, op.ctypes.data, d_recovery.data_ptr(),
+                                             r_row, r_b, rp.ctypes.data, d_restored.data_ptr(), x_row, x_b,
+                                             d_recovery_out.data_ptr(), y_row, y_b, codes, _stream(stream),
+                                             ctypes.byref(err))
+    if code == 7:  # (as decode_device_batch_masks: the stripe rides along as a plain attribute)
+        e = NotEnoughShards(**{f: int(getattr(err, f)) for f in NotEnoughShards.fields})
+        e.stripe = int(err.index)
+        raise e
+    _raise(code, err)
+    if status:
+        import numpy as np
+
+        return np.frombuffer(codes, dtype=np.uint8).copy()
+    return None
 
 
 class DeviceCall:
