@@ -34,6 +34,8 @@
  *   batch decode with an erasure pattern per stripe)
  *   rs_repair_device (+ _strided, + _batch; rs_repair_device_batch_masks: a
  *   pattern per stripe): the decode that also rebuilds missing recovery shards
+ *   rs_update_device (+ _batch): a partial-stripe write applied to the recovery
+ *   shards in place, from the changed originals' deltas alone
  *
  * Thread-safety: a context may be shared by threads (like DefaultEngine:
  * Send + Sync, src/lib.rs:385-409): calls on one context are serialized on the
@@ -384,6 +386,81 @@ rs_status rs_repair_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t o
                                        void *d_recovery_out, uint64_t recovery_out_stride,
                                        uint64_t recovery_out_stripe_stride, uint8_t *stripe_status, void *stream,
                                        rs_error *err);
+
+/* ---- update: a partial-stripe write applied to the recovery shards ----
+ * The caller overwrites `count` of the original shards (usually one) and the
+ * recovery shards must follow, without the other originals on the device: a
+ * parity node holds a few recovery rows and receives the delta of the changed
+ * original.  The encode is GF(2^16)-linear per column, so
+ *   recovery_j(new) = recovery_j(old) ^ XOR_c G[j][index[c]] * (old_c ^ new_c)
+ * with G[j][i] = element j of the encoder's output for the unit stripe (original
+ * i = the element 1, every other original zero).
+ *   index: HOST array of `count` original indices; row c of d_old and of d_new
+ * (count rows of shard_bytes each) is the old / the new content of original
+ * index[c].  d_old == NULL: d_new already holds the deltas old ^ new.
+ *   d_recovery: recovery_count rows, updated in place (read, XOR, write).
+ * recovery_update: HOST mask of recovery_count bytes of 0/1, NULL = every row;
+ * rows marked 0 are neither read nor written (their memory need not exist
+ * beyond the address arithmetic).  d_old and d_new must NOT overlap d_recovery.
+ *   Strides (0 = shard_bytes), alignment and the byte-wise path as in the
+ * _strided calls; any even shard_bytes, block and tail layout of
+ * rs_encode_device.  rs_update_device_batch applies ONE index list and ONE
+ * mask to every stripe (stripe strides 0 = count / recovery_count rows), as
+ * rs_repair_device_batch does.  Asynchronous on `stream`, scratch per
+ * (context, stream).
+ *   Result: the selected recovery rows are byte-identical to rs_encode_device
+ * on the stripe with the `count` originals replaced; nothing else is written.
+ *   Errors, all before any device work, in this order: null context, d_new,
+ * d_recovery, or index with count > 0 -> RS_ERR_INVALID_ARGUMENT; rs_validate;
+ * the row strides; then the index list in order: index[c] >= original_count ->
+ * InvalidOriginalShardIndex (original_count, index), a repeated index ->
+ * DuplicateOriginalShardIndex (index).  count == 0, stripes == 0 or a mask that
+ * selects no row: RS_OK, nothing launched, the context not touched.
+ *   Routes.  count <= direct_max: one launch of k_update, which forms the deltas
+ * once per workgroup and multiplies them into every selected recovery row by
+ * the table of log G[j][c]; a batch is the same launch with the stripe as a
+ * grid dimension.  The table is built by the first call with a given (rate,
+ * original_count, recovery_count, index list) on a stream -- the encode of the
+ * unit stripe, 64 * ceil(count / 32) bytes per shard, by whatever route the
+ * shape takes -- and kept until another key arrives on that stream or
+ * rs_release_stream_scratch frees it; it depends neither on the data nor on
+ * the mask.  count > direct_max (and any count > 256): the delta stripe is
+ * built in zeroed scratch, encoded, and the selected rows XORed into
+ * d_recovery; the stripes of a batch run one after another.
+ *   rs_update_set_direct_max sets direct_max for the context (0 = always
+ * re-encode); RS_MI355X_UPDATE_DIRECT_MAX does the same at context creation.
+ *   Measured (tools/update_time.py, profiles/update/update_time.txt; 1024:1024,
+ * delta form, every recovery row, us per call; cold = a new index list every
+ * call, so the coefficient step is paid; encode = rs_encode_device on the full
+ * stripe, which a caller without all the originals cannot run):
+ *     shard   count   direct cold   direct warm   re-encode   encode
+ *     1 KiB       1          26.3          12.3        17.9     10.8
+ *     1 KiB       8          27.3          11.9        16.5     10.8
+ *     1 KiB      16          29.3          11.2        19.1     10.7
+ *     1 KiB      32          34.2          12.9        16.8     10.5
+ *     1 KiB      64          44.0          22.3        16.6     10.9
+ *    64 KiB       1          55.5          33.1       149.9     98.9
+ *    64 KiB       8          99.8          79.2       150.4     97.8
+ *    64 KiB      16         159.9         139.5       152.0     98.3
+ *    64 KiB      32         359.0         338.6       153.2     98.2
+ *    64 KiB      64         682.9         662.1       153.5     98.4
+ * 64-stripe batch, 1 KiB, count 1: direct 32.3, re-encode 971, batch encode 224.
+ * The default direct_max, 16, is the largest measured count at which the warm
+ * direct route is still the faster of the two routes at both shard sizes; from
+ * count 16 on at 64 KiB it costs more than the full encode.  The whole table
+ * and what it says: DESIGN.md "Update". */
+#define RS_UPDATE_DIRECT_MAX_DEFAULT 16
+rs_status rs_update_device(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                           uint64_t shard_bytes, const uint64_t *index, uint64_t count, const void *d_old,
+                           uint64_t old_stride, const void *d_new, uint64_t new_stride, void *d_recovery,
+                           uint64_t recovery_stride, const uint8_t *recovery_update, void *stream, rs_error *err);
+rs_status rs_update_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                 uint64_t shard_bytes, uint64_t stripes, const uint64_t *index, uint64_t count,
+                                 const void *d_old, uint64_t old_stride, uint64_t old_stripe_stride,
+                                 const void *d_new, uint64_t new_stride, uint64_t new_stripe_stride,
+                                 void *d_recovery, uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                 const uint8_t *recovery_update, void *stream, rs_error *err);
+rs_status rs_update_set_direct_max(rs_context *ctx, uint32_t k);
 
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x

@@ -152,6 +152,21 @@ struct PinnedBuf {
     }
 };
 
+// What rs_update_device* keeps per stream (DESIGN.md "Update"): its scratch, the
+// index / row lists on the device with their host mirror, and the coefficient
+// table with the key it was built for.  A call whose lists or key match skips
+// the copy / the coefficient step.
+struct UpdateWs {
+    DevBuf unit, coef, logs, d_lists, delta, enc;
+    PinnedBuf h_lists;
+    std::vector<uint32_t> lists;  // what d_lists holds: the index list, then the selected rows
+    bool lists_valid = false;
+    bool coef_valid = false;  // `logs` holds the table of (coef_high, coef_n, coef_m, coef_index)
+    int coef_high = 0;
+    uint64_t coef_n = 0, coef_m = 0;
+    std::vector<uint32_t> coef_index;
+};
+
 // Device scratch of one stream's calls.  Calls on one stream execute in order,
 // so one workspace per (context, stream) makes concurrent calls on different
 // streams safe (rs_mi355x.h "Threading and streams").
@@ -159,7 +174,9 @@ struct Workspace {
     DevBuf buf[4], rowinfo, state;
     std::vector<uint8_t> h_state;
     PinnedBuf h_state_pinned;  // source of the erasure-state copy of large decodes
+    std::unique_ptr<UpdateWs> upd;  // rs_update_device*, made by the stream's first update
     void swap(Workspace &o) {
+        upd.swap(o.upd);
         for (int k = 0; k < 4; ++k) buf[k].swap(o.buf[k]);
         rowinfo.swap(o.rowinfo);
         state.swap(o.state);
@@ -325,6 +342,11 @@ struct rs_context {
     bool pad_small = true;        // decodes of 16..64 work rows on the 2^7-row column kernel (RS_MI355X_PAD_SMALL)
     int chunk_par = -1;           // RS_MI355X_CHUNK_PARALLEL: -1 by pack count (chunk_parallel), 0 / 1 forced
     uint32_t *d_lut2 = nullptr;   // perm2_by_log: the 2-element form of d_lut
+    // rs_update_device*: the log table (uploaded by the context's first update) and the
+    // largest count that takes the direct route (rs_update_set_direct_max,
+    // RS_MI355X_UPDATE_DIRECT_MAX; the default is measured: DESIGN.md "Update")
+    uint16_t *d_log = nullptr;
+    uint32_t update_direct_max = RS_UPDATE_DIRECT_MAX_DEFAULT;
     // the pass kernels' tables as 8-word bases (rs_kernels.hip BasisStager; RS_MI355X_PASS_BASIS=1).
     // Off by default: within +-2.5 % of the 20-word tables on 9 pass shapes, slower on the small
     // ones (4096:4096 x 1 KiB decode 100 % 39.4 -> 40.3 us, 8192:8192 x 64 KiB encode 1028 ->
@@ -1721,6 +1743,123 @@ void repair_masks_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, 
     decode_masks_dev(ctx, ws, high, g, N, M, orig, orig_present, rec, rec_present, restored, skip, s, rec_out);
 }
 
+// ---------------------------------------------------------------------------
+// update (rs_update_device*): recovery_j ^= XOR_c G[j][index_c] * (old_c ^ new_c)
+
+// The direct route's coefficient scratch is original_count x 64 * ceil(count / 32)
+// bytes, and k_update is quadratic: counts above this always re-encode.
+constexpr uint32_t kUpdateDirectCap = 256;
+
+template <typename F>
+void update_launch(hipStream_t s, uint64_t bytes, F &&launch) {
+    hipEvent_t ev = nullptr;
+    if (t_prof_ctx) prof_begin(s, &ev);
+    check(launch());
+    if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), bytes);
+}
+
+struct UpdateCall {
+    uint64_t N, M, S, count, stripes;
+    const uint64_t *index;
+    const uint8_t *d_old, *d_new;
+    uint8_t *d_rec;
+    uint64_t old_stride, new_stride, rec_stride;     // row strides, bytes
+    uint64_t old_bstride, new_bstride, rec_bstride;  // stripe strides, bytes
+    const uint8_t *mask;                             // nullptr: every recovery row
+};
+
+void update_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const UpdateCall &U, hipStream_t s) {
+    if (!ws.upd) ws.upd.reset(new UpdateWs);
+    UpdateWs &u = *ws.upd;
+    const uint32_t count = uint32_t(U.count);
+    // the lists on the device: the index list, then the selected rows (none when all are)
+    std::vector<uint32_t> lists(U.index, U.index + count);
+    for (uint64_t j = 0; U.mask && j < U.M; ++j)
+        if (U.mask[j]) lists.push_back(uint32_t(j));
+    uint32_t nsel = U.mask ? uint32_t(lists.size()) - count : uint32_t(U.M);
+    if (nsel == U.M) lists.resize(count);
+    if (!u.lists_valid || u.lists != lists) {
+        u.lists_valid = false;
+        const size_t bytes = lists.size() * 4;
+        uint8_t *h = u.h_lists.get(bytes);
+        std::memcpy(h, lists.data(), bytes);
+        check(hipMemcpyAsync(u.d_lists.get(bytes), h, bytes, hipMemcpyHostToDevice, s));
+        u.h_lists.copied_on(s);
+        u.lists = lists;
+        u.lists_valid = true;
+    }
+    const uint32_t *d_index = static_cast<const uint32_t *>(u.d_lists.p);
+    const uint32_t *d_rows = nsel == U.M ? nullptr : d_index + count;
+    const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+    auto encode = [&](const Geom &ge, const uint8_t *in, uint8_t *out) {
+        if (high) encode_high(ctx, ws, ge, U.N, U.M, in, out, s);
+        else encode_low(ctx, ws, ge, U.N, U.M, in, out, s);
+    };
+
+    if (count <= std::min(ctx->update_direct_max, kUpdateDirectCap)) {
+        if (!ctx->d_log) {  // the context's first update
+            const rs::GfTables &T = rs::tables();
+            check(hipMalloc(&ctx->d_log, T.log.size() * 2));
+            check(hipMemcpy(ctx->d_log, T.log.data(), T.log.size() * 2, hipMemcpyHostToDevice));
+        }
+        const std::vector<uint32_t> key(lists.begin(), lists.begin() + count);
+        if (!u.coef_valid || u.coef_high != int(high) || u.coef_n != U.N || u.coef_m != U.M || u.coef_index != key) {
+            u.coef_valid = false;
+            const uint64_t W = 64 * ((uint64_t(count) + 31) / 32);
+            uint8_t *unit = static_cast<uint8_t *>(u.unit.get(U.N * W));
+            uint8_t *coef = static_cast<uint8_t *>(u.coef.get(U.M * W));
+            uint16_t *logs = static_cast<uint16_t *>(u.logs.get(round_up(U.M * count * 2, 4)));
+            check(hipMemsetAsync(unit, 0, U.N * W, s));
+            update_launch(s, count, [&] { return rs::launch_update_unit(unit, W, d_index, count, s); });
+            encode(device_geom(W, 0, 0, 0, {unit, coef}), unit, coef);
+            update_launch(s, U.M * count * 4,
+                          [&] { return rs::launch_update_log(coef, W, uint32_t(U.M), count, ctx->d_log, logs, s); });
+            u.coef_high = int(high), u.coef_n = U.N, u.coef_m = U.M, u.coef_index = key;
+            u.coef_valid = true;
+        }
+        rs::UpdateArgs A;
+        A.old_stride = U.old_stride, A.new_stride = U.new_stride, A.rec_stride = U.rec_stride;
+        A.old_bstride = U.old_bstride, A.new_bstride = U.new_bstride, A.rec_bstride = U.rec_bstride;
+        A.packs = g.packs, A.count = count, A.nsel = nsel;
+        A.rows = d_rows;
+        A.logs = static_cast<const uint16_t *>(u.logs.p);
+        A.lut = ctx->d_lut;
+        A.fmt = g.fmt;
+        for (uint64_t b0 = 0; b0 < U.stripes; b0 += kMaxBatchStripes) {  // grid.z limit
+            A.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, U.stripes - b0));
+            A.old_rows = U.d_old ? U.d_old + b0 * U.old_bstride : nullptr;
+            A.new_rows = U.d_new + b0 * U.new_bstride;
+            A.rec = U.d_rec + b0 * U.rec_bstride;
+            const uint64_t rows = 2 * uint64_t(nsel) + uint64_t(count) * (U.d_old ? 2 : 1);
+            update_launch(s, rows * pack_bytes * A.stripes, [&] { return rs::launch_update(A, s); });
+        }
+        return;
+    }
+
+    // re-encode: the delta stripe (zero but for the changed rows), its encode, and the
+    // selected rows of that XORed into the recovery matrix; one stripe after another
+    const uint64_t W = g.stride;
+    uint8_t *delta = static_cast<uint8_t *>(u.delta.get(U.N * W));
+    uint8_t *enc = static_cast<uint8_t *>(u.enc.get(U.M * W));
+    const Geom ge = device_geom(U.S, W, W, W, {delta, enc}, W);
+    for (uint64_t b = 0; b < U.stripes; ++b) {
+        check(hipMemsetAsync(delta, 0, U.N * W, s));
+        rs::UpdateXorArgs X;
+        X.packs = g.packs, X.fmt = g.fmt, X.list = d_index, X.nrows = count;
+        X.out = delta, X.out_stride = W, X.out_list = 1;
+        X.a = U.d_new + b * U.new_bstride, X.a_stride = U.new_stride;
+        X.b = U.d_old ? U.d_old + b * U.old_bstride : nullptr, X.b_stride = U.old_stride;
+        update_launch(s, uint64_t(count) * (U.d_old ? 3 : 2) * pack_bytes, [&] { return rs::launch_update_xor(X, s); });
+        encode(ge, delta, enc);
+        rs::UpdateXorArgs Y;
+        Y.packs = g.packs, Y.fmt = g.fmt, Y.list = d_rows, Y.nrows = nsel;
+        Y.out = U.d_rec + b * U.rec_bstride, Y.out_stride = U.rec_stride, Y.out_list = 1;
+        Y.a = Y.out, Y.a_stride = U.rec_stride, Y.a_list = 1;
+        Y.b = enc, Y.b_stride = W, Y.b_list = 1;
+        update_launch(s, uint64_t(nsel) * 3 * pack_bytes, [&] { return rs::launch_update_xor(Y, s); });
+    }
+}
+
 const char *hip_msg(hipError_t e) { return hipGetErrorString(e); }
 
 }  // namespace
@@ -1976,6 +2115,7 @@ rs_status rs_context_create(int device, rs_context **out) {
         ctx->half_default = ctx->half;
         if (const char *qs = getenv("RS_MI355X_QUAD")) ctx->quad = qs[0] == '1';
         if (const char *cp = getenv("RS_MI355X_COPYIN_POOL")) ctx->copyin_pool = cp[0] == '1';
+        if (const char *ud = getenv("RS_MI355X_UPDATE_DIRECT_MAX")) ctx->update_direct_max = uint32_t(strtoul(ud, nullptr, 10));
         ctx->quad_default = ctx->quad;
         if (const char *ck = getenv("RS_MI355X_CHUNKS")) {  // 0 off, 1 default routing, 2 every supported shape
             ctx->chunks = ck[0] != '0';
@@ -2036,6 +2176,7 @@ void rs_context_destroy(rs_context *ctx) {
     if (ctx->d_tw) (void)hipFree(ctx->d_tw);
     if (ctx->d_lut) (void)hipFree(ctx->d_lut);
     if (ctx->d_lut2) (void)hipFree(ctx->d_lut2);
+    if (ctx->d_log) (void)hipFree(ctx->d_log);
     if (ctx->d_twb) (void)hipFree(ctx->d_twb);
     if (ctx->d_lutb) (void)hipFree(ctx->d_lutb);
     if (ctx->d_top) (void)hipFree(ctx->d_top);
@@ -2593,6 +2734,76 @@ rs_status rs_repair_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
         }
         return set_err(err, RS_OK);
     });
+}
+
+// ---- update: a partial-stripe write applied to the recovery shards (include/rs_mi355x.h) ----
+
+rs_status rs_update_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, uint64_t stripes,
+                                 const uint64_t *index, uint64_t count, const void *d_old, uint64_t old_stride,
+                                 uint64_t old_stripe_stride, const void *d_new, uint64_t new_stride,
+                                 uint64_t new_stripe_stride, void *d_recovery, uint64_t recovery_stride,
+                                 uint64_t recovery_stripe_stride, const uint8_t *recovery_update, void *stream,
+                                 rs_error *err) {
+    if (!ctx || !ptr_ok(d_new) || !ptr_ok(d_recovery) || (!index && count > 0))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if ((d_old && !stride_ok(old_stride, S)) || !stride_ok(new_stride, S) || !stride_ok(recovery_stride, S))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    {  // the index list, in order (a list longer than original_count holds one of the two)
+        std::vector<uint8_t> seen(N, 0);
+        for (uint64_t c = 0; c < count; ++c) {
+            const uint64_t i = index[c];
+            if (i >= N) {
+                set_err(err, RS_ERR_INVALID_ORIGINAL_SHARD_INDEX);
+                if (err) err->original_count = N, err->index = i;
+                return RS_ERR_INVALID_ORIGINAL_SHARD_INDEX;
+            }
+            if (seen[i]) {
+                set_err(err, RS_ERR_DUPLICATE_ORIGINAL_SHARD_INDEX);
+                if (err) err->index = i;
+                return RS_ERR_DUPLICATE_ORIGINAL_SHARD_INDEX;
+            }
+            seen[i] = 1;
+        }
+    }
+    // nothing to change: nothing launched, nothing written, the context not touched
+    bool any = recovery_update == nullptr;
+    for (uint64_t j = 0; !any && j < M; ++j) any = recovery_update[j] != 0;
+    if (count == 0 || stripes == 0 || !any) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, d_old ? old_stride : 0, new_stride, recovery_stride, {d_old, d_new, d_recovery});
+        UpdateCall U{N, M, S, count, stripes, index, static_cast<const uint8_t *>(d_old),
+                     static_cast<const uint8_t *>(d_new), static_cast<uint8_t *>(d_recovery),
+                     g.orig(), g.rec(), g.out(), 0, 0, 0, recovery_update};
+        U.old_bstride = old_stripe_stride ? old_stripe_stride : count * U.old_stride;
+        U.new_bstride = new_stripe_stride ? new_stripe_stride : count * U.new_stride;
+        U.rec_bstride = recovery_stripe_stride ? recovery_stripe_stride : M * U.rec_stride;
+        if (stripes > 1 && ((d_old ? U.old_bstride : 0) | U.new_bstride | U.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        update_dev(ctx, sw.w, high != 0, g, U, s);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_update_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const uint64_t *index,
+                           uint64_t count, const void *d_old, uint64_t old_stride, const void *d_new,
+                           uint64_t new_stride, void *d_recovery, uint64_t recovery_stride,
+                           const uint8_t *recovery_update, void *stream, rs_error *err) {
+    return rs_update_device_batch(ctx, rate, N, M, S, 1, index, count, d_old, old_stride, 0, d_new, new_stride, 0,
+                                  d_recovery, recovery_stride, 0, recovery_update, stream, err);
+}
+
+rs_status rs_update_set_direct_max(rs_context *ctx, uint32_t k) {
+    if (!ctx) return RS_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->update_direct_max = k;
+    return RS_OK;
 }
 
 // ---- encoder ----------------------------------------------------------------

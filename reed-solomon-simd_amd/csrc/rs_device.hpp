@@ -382,6 +382,49 @@ struct EvalArgs {
 };
 hipError_t launch_eval_poly(const EvalArgs &A, hipStream_t stream);
 
+// ---- update (rs_update_device*, rs_update.hip; DESIGN.md "Update") ----------
+// Coefficient step.  launch_update_unit writes the unit stripe into zeroed
+// rows of `stride` = 64 * ceil(count / 32) bytes: element c of row index[c] = 1
+// (low byte 1 at offset c % 32 of block c / 32).  launch_update_log turns the
+// encode of that stripe (`coef`, rows of `stride` bytes) into logs[j * count + c]
+// = log of element c of recovery row j; element 0 becomes kUpdateNoCoef.
+constexpr uint32_t kUpdateNoCoef = 65535;  // (log[0] of the host table: no multiplier has this log)
+hipError_t launch_update_unit(uint8_t *unit, uint64_t stride, const uint32_t *index, uint32_t count, hipStream_t stream);
+hipError_t launch_update_log(const uint8_t *coef, uint64_t stride, uint32_t rows, uint32_t count,
+                             const uint16_t *log_table, uint16_t *logs, hipStream_t stream);
+// The direct update (k_update): for every selected recovery row j (rows[r], r <
+// nsel; rows = nullptr: row r) and every pack, recovery_j ^= XOR_c delta_c *
+// exp(logs[j * count + c]), delta_c = old_c ^ new_c (old = nullptr: new_c).
+// grid = (pack tiles, row groups, stripes); the deltas are formed once per
+// workgroup and, for count <= kUpdateTile, stay in registers across its rows.
+constexpr uint32_t kUpdateTile = 16;
+struct UpdateArgs {
+    const uint8_t *old_rows = nullptr, *new_rows = nullptr;  // count rows each
+    uint8_t *rec = nullptr;
+    uint64_t old_stride = 0, new_stride = 0, rec_stride = 0;
+    uint64_t old_bstride = 0, new_bstride = 0, rec_bstride = 0;  // stripe b: + b * bstride
+    uint32_t packs = 0, count = 0, nsel = 0, stripes = 1;
+    uint32_t rows_per_group = 1;
+    const uint32_t *rows = nullptr;
+    const uint16_t *logs = nullptr;  // 4-byte aligned
+    const uint32_t *lut = nullptr;   // perm tables by log factor (rs_context::d_lut)
+    ShardFormat fmt;
+};
+hipError_t launch_update(const UpdateArgs &A, hipStream_t stream);
+// Row-wise XOR over a row list (the re-encode route's two ends): for r < nrows,
+// out row (out_list ? list[r] : r) = a row (a_list ? list[r] : r) ^ b row (b_list
+// ? list[r] : r); b = nullptr: a copy of the a row.  list = nullptr: row r everywhere.
+struct UpdateXorArgs {
+    uint8_t *out = nullptr;
+    const uint8_t *a = nullptr, *b = nullptr;
+    uint64_t out_stride = 0, a_stride = 0, b_stride = 0;
+    const uint32_t *list = nullptr;
+    uint32_t out_list = 0, a_list = 0, b_list = 0;
+    uint32_t nrows = 0, packs = 0;
+    ShardFormat fmt;
+};
+hipError_t launch_update_xor(const UpdateXorArgs &A, hipStream_t stream);
+
 // x[rows] *= exp(log_m) over `blocks` 64-byte blocks.
 hipError_t launch_mul(uint8_t *rows, uint64_t blocks, const uint32_t *lut_entry, hipStream_t stream);
 

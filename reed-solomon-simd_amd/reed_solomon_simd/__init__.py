@@ -111,6 +111,11 @@ _sig("rs_repair_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u6
      _u64, ctypes.c_char_p, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _E)
 _sig("rs_repair_device_batch_masks", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _u64, _u64,
      _vp, _vp, _u64, _u64, _vp, _u64, _u64, ctypes.POINTER(ctypes.c_uint8), _vp, _E)
+_sig("rs_update_device", _int, _vp, _int, _u64, _u64, _u64, ctypes.POINTER(_u64), _u64, _vp, _u64, _vp, _u64, _vp, _u64,
+     ctypes.c_char_p, _vp, _E)
+_sig("rs_update_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, ctypes.POINTER(_u64), _u64, _vp, _u64, _u64, _vp,
+     _u64, _u64, _vp, _u64, _u64, ctypes.c_char_p, _vp, _E)
+_sig("rs_update_set_direct_max", _int, _vp, ctypes.c_uint32)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -985,6 +990,75 @@ def repair_device_batch_masks(original_count: int, recovery_count: int, shard_by
 
         return np.frombuffer(codes, dtype=np.uint8).copy()
     return None
+
+
+UPDATE_DIRECT_MAX_DEFAULT = 16  # RS_UPDATE_DIRECT_MAX_DEFAULT (include/rs_mi355x.h)
+
+
+def _index_list(indices):
+    """A host list of original indices as a C uint64 array (the library checks range and repeats)."""
+    idx = [int(i) for i in indices]
+    if any(i < 0 for i in idx):
+        raise ValueError("indices: an original index cannot be negative")
+    return (_u64 * len(idx))(*idx), len(idx)
+
+
+def update_device(original_count: int, recovery_count: int, shard_bytes: int, indices, d_old, d_new, d_recovery,
+                  recovery_rows=None, stream=None, rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None) -> None:
+    """Apply a partial-stripe write to the recovery shards in place (rs_update_device): row c of
+    d_old / d_new [len(indices), shard_bytes] is the old / new content of original indices[c];
+    d_old=None: d_new holds the deltas old ^ new.  d_recovery [recovery_count, shard_bytes] ends
+    byte-identical to encode_device on the changed stripe.  recovery_rows: recovery_count flags,
+    0 = leave that row alone (neither read nor written); None = every row.  d_old and d_new must
+    not overlap d_recovery."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    idx, k = _index_list(indices)
+    rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
+                                                          "recovery_rows")
+    if d_old is not None:
+        _check_matrix(d_old, k, shard_bytes, "d_old")
+    _check_matrix(d_new, k, shard_bytes, "d_new")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    err = _RsError()
+    _raise(_lib.rs_update_device(ctx.handle, rate_, original_count, recovery_count, shard_bytes, idx, k,
+                                 None if d_old is None else _ptr(d_old), 0 if d_old is None else _row_stride(d_old),
+                                 _ptr(d_new), _row_stride(d_new), _ptr(d_recovery), _row_stride(d_recovery), rows,
+                                 _stream(stream), ctypes.byref(err)), err)
+
+
+def update_device_batch(original_count: int, recovery_count: int, shard_bytes: int, indices, d_old, d_new,
+                        d_recovery, recovery_rows=None, stream=None, rate_: int = RATE_DEFAULT,
+                        ctx: Optional[Context] = None) -> None:
+    """update_device on a batch of stripes sharing ONE index list and ONE row mask
+    (rs_update_device_batch); tensors [stripes, rows, shard_bytes]."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    idx, k = _index_list(indices)
+    rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
+                                                          "recovery_rows")
+    if d_old is not None:
+        _check_matrix(d_old, k, shard_bytes, "d_old", 3)
+    _check_matrix(d_new, k, shard_bytes, "d_new", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_new.shape[0]
+    if d_recovery.shape[0] != n or (d_old is not None and d_old.shape[0] != n):
+        raise ValueError("batches differ in stripe count")
+    (o_row, o_b) = (0, 0) if d_old is None else _batch_strides(d_old)
+    (n_row, n_b), (r_row, r_b) = _batch_strides(d_new), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_update_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n, idx, k,
+                                       None if d_old is None else d_old.data_ptr(), o_row, o_b, d_new.data_ptr(),
+                                       n_row, n_b, d_recovery.data_ptr(), r_row, r_b, rows, _stream(stream),
+                                       ctypes.byref(err)), err)
+
+
+def update_set_direct_max(k: int, ctx: Optional[Context] = None) -> None:
+    """Largest len(indices) that update_device runs as one k_update launch; above it the delta
+    stripe is re-encoded (rs_update_set_direct_max; 0 = always re-encode)."""
+    ctx = ctx or default_context()
+    if _lib.rs_update_set_direct_max(ctx.handle, int(k)) != 0:
+        raise ValueError("invalid argument (rs_status 101)")
 
 
 class DeviceCall:
