@@ -462,6 +462,81 @@ rs_status rs_update_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  const uint8_t *recovery_update, void *stream, rs_error *err);
 rs_status rs_update_set_direct_max(rs_context *ctx, uint32_t k);
 
+/* ---- verify: do the recovery shards still agree with the originals? ----
+ * The first step of a scrub.  Silent corruption (a flipped bit on a disk or in a
+ * buffer) is not an erasure, so rs_repair_device* cannot see it; this call finds
+ * the recovery rows to hand to it as absent.
+ *   d_original: original_count rows, all present.  d_recovery: recovery_count
+ * rows.  recovery_check: HOST mask of recovery_count bytes of 0/1, NULL = every
+ * row; rows marked 0 are never read (a degraded stripe is checked on the recovery
+ * rows it still has; the memory of the others need not exist beyond the address
+ * arithmetic).  d_mismatch: DEVICE array of recovery_count bytes
+ * (rs_verify_device_batch: stripes x recovery_count, stripe-major, dense).
+ *   Result: after the call every byte of d_mismatch is defined.  Byte
+ * b * recovery_count + j is 1 if row j is selected and recovery shard j of stripe
+ * b differs, in any of its shard_bytes bytes, from what rs_encode_device would
+ * produce from that stripe's originals (block and tail layout of the encode); 0
+ * if the row matches and 0 if it is not selected.  Nothing else is written: not
+ * the originals, not the recovery shards, not a byte past stripes x
+ * recovery_count of the flags.  Bytes between shard_bytes and the row stride are
+ * never compared.
+ *   Strides (0 = shard_bytes / count rows), alignment and the byte-wise path for
+ * unaligned bases or strides as in the _strided / _batch calls.
+ * rs_verify_device_batch applies ONE mask to every stripe, as
+ * rs_update_device_batch does.  Asynchronous on `stream`, scratch per (context,
+ * stream).
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * d_recovery or d_mismatch -> RS_ERR_INVALID_ARGUMENT; rs_validate; the two row
+ * strides.  stripes == 0: RS_OK, nothing launched or written, the context not
+ * touched.  A mask that selects no row: RS_OK, no kernel, no workspace, the
+ * context not touched -- the flags are zeroed by one hipMemsetAsync on `stream`
+ * (stripes x recovery_count bytes), so they are defined after this call too; if
+ * that memset fails the call returns RS_ERR_DEVICE.
+ *   Routes.  Every call first zeroes the flags on `stream`; the kernels store
+ * only the ones (plain byte stores of the same value, no atomics).
+ *   Fused (k_mono_verify): where the encode is the staged single-chunk column
+ * kernel (2^7..2^11 transform rows, at most 256 packs, either rate, 2- and
+ * 4-element packs -- the shapes whose batch encode is one launch) the encode's
+ * last step loads the caller's word from the address it would have stored to,
+ * compares and flags.  One launch per 65535 stripes, no scratch matrix.  With a
+ * mask the destination map is narrowed to the span of the selected rows and a
+ * selection array, kept with the stream's scratch and copied on `stream` only
+ * when the mask changes, says which rows inside the span are compared.  The
+ * lane and quad encode kernels have no verify form: the column kernel runs in
+ * their place.
+ *   Unfused (every shape the encode supports): the encode of the selected span
+ * into per-stream scratch (recovery_count rows per stripe: the whole batch where
+ * the batch encode is one launch, else stripe by stripe), then k_verify_rows
+ * compares scratch and caller rows over the row list.
+ *   rs_verify_set_fused: 0 = never fused, 1 = fused where available;
+ * RS_MI355X_VERIFY_FUSED does the same at context creation.
+ *   Measured (tools/verify_time.py, profiles/verify/verify_time.txt; 1024:1024,
+ * every row, us per call; encode = rs_encode_device[_batch] of the same shape,
+ * whose kernels are the parent commit's instruction for instruction -- the leg
+ * run on the parent's build read 8.38 / 224.4 / 102.1; spread = max - min of the
+ * encode leg's five rounds):
+ *     shape                 fused   unfused   encode   spread   fused/encode
+ *     1 KiB, one stripe     10.65     13.05     8.88     0.57   1.20 (+1.77 us)
+ *     1 KiB, 64 stripes     241.2     254.4    223.9     1.73   1.08 (+17.2 us)
+ *     64 KiB, one stripe       --     124.3     97.9     7.19   (unfused 1.27)
+ * The fused verify was expected to land within the encode's spread; it is
+ * outside it, by 1.2 us at one stripe (the memset of the flags is a dispatch of
+ * its own) and by 15.5 us over 64 stripes (a load must come back where a store
+ * need not: the kernel is 7 % slower than the encode's).  It is no slower than
+ * the unfused route at either shape (0.82, 0.95) and needs no scratch matrix,
+ * so the default is 1.  DESIGN.md "Verify" has the rest. */
+#define RS_VERIFY_FUSED_DEFAULT 1
+rs_status rs_verify_device(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                           uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
+                           const void *d_recovery, uint64_t recovery_stride, const uint8_t *recovery_check,
+                           uint8_t *d_mismatch, void *stream, rs_error *err);
+rs_status rs_verify_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                 uint64_t shard_bytes, uint64_t stripes, const void *d_original,
+                                 uint64_t original_stride, uint64_t original_stripe_stride, const void *d_recovery,
+                                 uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                 const uint8_t *recovery_check, uint8_t *d_mismatch, void *stream, rs_error *err);
+rs_status rs_verify_set_fused(rs_context *ctx, int mode);
+
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x
  * shard_bytes) are row-major HOST matrices; pinned memory (rs_host_alloc,

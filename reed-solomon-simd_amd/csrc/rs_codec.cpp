@@ -167,6 +167,18 @@ struct UpdateWs {
     std::vector<uint32_t> coef_index;
 };
 
+// What rs_verify_device* keeps per stream (DESIGN.md "Verify"): the scratch matrix
+// of the unfused route and the caller's mask on the device -- recovery_count
+// selection bytes (the fused kernel reads them), padded to a word, then the list
+// of the selected rows (k_verify_rows reads it) -- with its host mirror.  A call
+// whose mask matches skips the copy.
+struct VerifyWs {
+    DevBuf enc, d_mask;
+    PinnedBuf h_mask;
+    std::vector<uint8_t> mask;  // what d_mask was built from, as 0/1 bytes
+    bool mask_valid = false;
+};
+
 // Device scratch of one stream's calls.  Calls on one stream execute in order,
 // so one workspace per (context, stream) makes concurrent calls on different
 // streams safe (rs_mi355x.h "Threading and streams").
@@ -175,8 +187,10 @@ struct Workspace {
     std::vector<uint8_t> h_state;
     PinnedBuf h_state_pinned;  // source of the erasure-state copy of large decodes
     std::unique_ptr<UpdateWs> upd;  // rs_update_device*, made by the stream's first update
+    std::unique_ptr<VerifyWs> ver;  // rs_verify_device*, made by the stream's first masked or unfused verify
     void swap(Workspace &o) {
         upd.swap(o.upd);
+        ver.swap(o.ver);
         for (int k = 0; k < 4; ++k) buf[k].swap(o.buf[k]);
         rowinfo.swap(o.rowinfo);
         state.swap(o.state);
@@ -347,6 +361,10 @@ struct rs_context {
     // RS_MI355X_UPDATE_DIRECT_MAX; the default is measured: DESIGN.md "Update")
     uint16_t *d_log = nullptr;
     uint32_t update_direct_max = RS_UPDATE_DIRECT_MAX_DEFAULT;
+    // rs_verify_device*: the fused route (k_mono_verify) where the encode is the staged
+    // single-chunk column kernel (rs_verify_set_fused, RS_MI355X_VERIFY_FUSED; the
+    // default is measured: DESIGN.md "Verify")
+    bool verify_fused = RS_VERIFY_FUSED_DEFAULT != 0;
     // the pass kernels' tables as 8-word bases (rs_kernels.hip BasisStager; RS_MI355X_PASS_BASIS=1).
     // Off by default: within +-2.5 % of the 20-word tables on 9 pass shapes, slower on the small
     // ones (4096:4096 x 1 KiB decode 100 % 39.4 -> 40.3 us, 8192:8192 x 64 KiB encode 1028 ->
@@ -1860,6 +1878,104 @@ void update_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
     }
 }
 
+// ---- verify (rs_verify_device*, DESIGN.md "Verify") -------------------------
+struct VerifyCall {
+    uint64_t N, M, S, stripes;
+    const uint8_t *d_orig, *d_rec;
+    uint64_t orig_bstride, rec_bstride;  // stripe strides, bytes (row strides: the Geom's)
+    const uint8_t *mask;                 // nullptr: every recovery row
+    uint8_t *d_flags;                    // stripes x M
+};
+
+// The caller has checked that the mask selects a row and that stripes > 0.
+void verify_dev(rs_context *ctx, Workspace &ws, bool high, Geom g, const VerifyCall &V, hipStream_t s) {
+    const uint32_t M = uint32_t(V.M);
+    uint32_t lo = 0, hi = M, nsel = M;  // the span of the selected rows and their number
+    if (V.mask) {
+        lo = M, hi = 0, nsel = 0;
+        for (uint32_t j = 0; j < M; ++j)
+            if (V.mask[j]) lo = std::min(lo, j), hi = j + 1, ++nsel;
+    }
+    // every flag is defined after the call: zero, then the kernels store the ones
+    check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
+    const uint8_t *d_sel = nullptr;    // M selection bytes (the fused kernel)
+    const uint32_t *d_list = nullptr;  // the nsel selected rows (k_verify_rows)
+    if (nsel < M) {
+        if (!ws.ver) ws.ver.reset(new VerifyWs);
+        VerifyWs &v = *ws.ver;
+        std::vector<uint8_t> mask(M);
+        for (uint32_t j = 0; j < M; ++j) mask[j] = V.mask[j] != 0;
+        const size_t list_off = round_up(M, 4), bytes = list_off + size_t(nsel) * 4;
+        if (!v.mask_valid || v.mask != mask) {
+            v.mask_valid = false;
+            uint8_t *h = v.h_mask.get(bytes);
+            std::memcpy(h, mask.data(), M);
+            uint32_t *list = reinterpret_cast<uint32_t *>(h + list_off);
+            for (uint32_t j = 0, k = 0; j < M; ++j)
+                if (mask[j]) list[k++] = j;
+            check(hipMemcpyAsync(v.d_mask.get(bytes), h, bytes, hipMemcpyHostToDevice, s));
+            v.h_mask.copied_on(s);
+            v.mask.swap(mask);
+            v.mask_valid = true;
+        }
+        d_sel = static_cast<const uint8_t *>(v.d_mask.p);
+        d_list = reinterpret_cast<const uint32_t *>(d_sel + list_off);
+    }
+    // the encode's transform: does it run as the staged single-chunk column kernel
+    // (one launch for a batch, encode_high / encode_low)?
+    const uint32_t n = uint32_t(next_pow2(high ? V.M : V.N)), L = ilog2(n);
+    const uint32_t C = uint32_t(((high ? V.N : V.M) + n - 1) / n);
+    const bool column = use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+    const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+
+    if (column && ctx->verify_fused) {
+        for (uint64_t b0 = 0; b0 < V.stripes; b0 += kMaxBatchStripes) {  // grid.y limit
+            g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, V.stripes - b0));
+            const rs::MonoArgs Mo = mono_args(ctx, L, g, true);
+            rs::MonoVerifyArgs A;
+            static_cast<rs::MonoCore &>(A) = Mo;
+            A.src[0] = rs::RowMap{V.d_orig + b0 * V.orig_bstride, g.orig(), 0, uint32_t(V.N)};
+            A.src_bstride[0] = V.orig_bstride;
+            A.nsrc = 1;
+            A.dst = rs::RowMap{V.d_rec + b0 * V.rec_bstride + uint64_t(lo) * g.rec(), g.rec(), lo, hi};
+            A.dst_bstride = V.rec_bstride;
+            A.chunks = 1;
+            A.ifft_img = high ? 1 : 0;  // as encode_high / encode_low
+            A.fft_img = high ? 0 : 1;
+            A.ifft_img_step = high ? 1 : 0;
+            A.fft_img_step = high ? 0 : 1;
+            A.flags = V.d_flags + b0 * V.M + lo;
+            A.flag_bstride = V.M;
+            A.sel = nsel == hi - lo ? nullptr : d_sel + lo;
+            update_launch(s, (V.N + nsel) * pack_bytes * g.stripes, [&] { return rs::launch_mono_verify(int(L), A, s); });
+        }
+        return;
+    }
+
+    // unfused: the encode of the selected span into scratch, then the compare.  The
+    // whole batch at once where the encode takes it as one launch, else stripe by stripe
+    if (!ws.ver) ws.ver.reset(new VerifyWs);
+    const uint64_t W = g.stride, group = column ? kMaxBatchStripes : 1;
+    uint8_t *enc = static_cast<uint8_t *>(ws.ver->enc.get(std::min<uint64_t>(group, V.stripes) * V.M * W));
+    Geom ge = g;
+    ge.rec_stride = W;
+    ge.orig_bstride = V.orig_bstride;
+    ge.rec_bstride = V.M * W;
+    for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
+        ge.stripes = uint32_t(std::min<uint64_t>(group, V.stripes - b0));
+        const uint8_t *o = V.d_orig + b0 * V.orig_bstride;
+        if (high) encode_high(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
+        else encode_low(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
+        rs::VerifyRowsArgs R;
+        R.want = enc, R.want_stride = W, R.want_bstride = V.M * W;
+        R.have = V.d_rec + b0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
+        R.rows = d_list, R.nrows = nsel, R.packs = g.packs, R.stripes = ge.stripes;
+        R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
+        R.fmt = g.fmt;
+        update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(R, s); });
+    }
+}
+
 const char *hip_msg(hipError_t e) { return hipGetErrorString(e); }
 
 }  // namespace
@@ -2116,6 +2232,7 @@ rs_status rs_context_create(int device, rs_context **out) {
         if (const char *qs = getenv("RS_MI355X_QUAD")) ctx->quad = qs[0] == '1';
         if (const char *cp = getenv("RS_MI355X_COPYIN_POOL")) ctx->copyin_pool = cp[0] == '1';
         if (const char *ud = getenv("RS_MI355X_UPDATE_DIRECT_MAX")) ctx->update_direct_max = uint32_t(strtoul(ud, nullptr, 10));
+        if (const char *vf = getenv("RS_MI355X_VERIFY_FUSED")) ctx->verify_fused = atoi(vf) != 0;
         ctx->quad_default = ctx->quad;
         if (const char *ck = getenv("RS_MI355X_CHUNKS")) {  // 0 off, 1 default routing, 2 every supported shape
             ctx->chunks = ck[0] != '0';
@@ -2803,6 +2920,59 @@ rs_status rs_update_set_direct_max(rs_context *ctx, uint32_t k) {
     if (!ctx) return RS_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->update_direct_max = k;
+    return RS_OK;
+}
+
+// ---- verify: the recovery shards checked against the originals (include/rs_mi355x.h) ----
+
+rs_status rs_verify_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, uint64_t stripes,
+                                 const void *d_orig, uint64_t orig_stride, uint64_t orig_stripe_stride,
+                                 const void *d_rec, uint64_t rec_stride, uint64_t rec_stripe_stride,
+                                 const uint8_t *recovery_check, uint8_t *d_mismatch, void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_mismatch)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    bool any = recovery_check == nullptr;
+    for (uint64_t j = 0; !any && j < M; ++j) any = recovery_check[j] != 0;
+    if (!any) {
+        // no row to check: every flag is 0.  One memset on the caller's stream; no
+        // kernel, no workspace, the context not touched
+        return guarded(err, [&]() -> rs_status {
+            check(hipMemsetAsync(d_mismatch, 0, stripes * M, static_cast<hipStream_t>(stream)));
+            return set_err(err, RS_OK);
+        });
+    }
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                     0, 0, recovery_check, d_mismatch};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        verify_dev(ctx, sw.w, high != 0, g, V, s);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_verify_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const void *d_orig,
+                           uint64_t orig_stride, const void *d_rec, uint64_t rec_stride,
+                           const uint8_t *recovery_check, uint8_t *d_mismatch, void *stream, rs_error *err) {
+    return rs_verify_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
+                                  d_mismatch, stream, err);
+}
+
+rs_status rs_verify_set_fused(rs_context *ctx, int mode) {
+    if (!ctx) return RS_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->verify_fused = mode != 0;
     return RS_OK;
 }
 

@@ -425,6 +425,42 @@ struct UpdateXorArgs {
 };
 hipError_t launch_update_xor(const UpdateXorArgs &A, hipStream_t stream);
 
+// ---- verify (rs_verify_device*, rs_verify.hip; DESIGN.md "Verify") ----------
+// The fused route (k_mono_verify): the staged single-chunk column encode whose
+// store_col compares instead of storing.  dst is the caller's recovery matrix,
+// narrowed to the span of the selected rows; a lane loads the caller's word from
+// the address it would have stored to and, where it differs from the encoded
+// word, stores the byte 1 to flags[stripe * flag_bstride + (r - dst.row_begin)].
+// sel (nullptr: every row of dst): sel[r - dst.row_begin] != 0 = row r is
+// compared; the others are never read.  Row dst.row_begin must be selected (lanes
+// without a row of their own read it and discard it).  The kernel takes the
+// encode's MonoCore, not MonoArgs: the encodes have no erasure bitmaps, and
+// argument bytes cost launch time.
+struct MonoVerifyArgs : MonoCore {
+    uint8_t *flags = nullptr;
+    uint64_t flag_bstride = 0;
+    const uint8_t *sel = nullptr;
+};
+// Staged kernel only (mono_staged(L, 1): 7 <= L <= 11), A.chunks = 1, elems 2 or
+// 4, grid.y = A.stripes (>= 1).  The staged body is the same for both rates (they
+// differ in the images the host names), so one kernel per (L, elems) serves both.
+hipError_t launch_mono_verify(int L, const MonoVerifyArgs &A, hipStream_t stream);
+// The unfused route's compare (k_verify_rows): for r < nrows and every pack, row
+// j = rows ? rows[r] : r of `want` (the encode in scratch) against row j of `have`
+// (the caller's recovery matrix), both in the layout of fmt; a difference stores
+// the byte 1 to flags[stripe * flag_bstride + j].  grid = (pack tiles, nrows, stripes).
+struct VerifyRowsArgs {
+    const uint8_t *want = nullptr, *have = nullptr;
+    uint64_t want_stride = 0, have_stride = 0;
+    uint64_t want_bstride = 0, have_bstride = 0;  // stripe b: + b * bstride
+    const uint32_t *rows = nullptr;
+    uint32_t nrows = 0, packs = 0, stripes = 1;
+    uint8_t *flags = nullptr;
+    uint64_t flag_bstride = 0;
+    ShardFormat fmt;
+};
+hipError_t launch_verify_rows(const VerifyRowsArgs &A, hipStream_t stream);
+
 // x[rows] *= exp(log_m) over `blocks` 64-byte blocks.
 hipError_t launch_mul(uint8_t *rows, uint64_t blocks, const uint32_t *lut_entry, hipStream_t stream);
 

@@ -734,6 +734,18 @@ struct Dst2 {
 [[maybe_unused]] __device__ __forceinline__ bool in_map(const RowMap &m, uint32_t r) {
     return r - m.row_begin < m.row_end - m.row_begin;
 }
+// A verify (rs_device.hpp MonoVerifyArgs; VERIFY): this workgroup's stripe's flag of
+// row A.dst.row_begin, the selection of the rows of A.dst, and the caller's words
+// of the lane's rows, requested in the prologue (verify_select / verify_issue) and
+// compared by store_col.  The encode's instantiations (VERIFY = false) never touch it.
+template <int LR>
+struct VerifyPre {
+    uint8_t *flags = nullptr;
+    const uint8_t *sel = nullptr;
+    uint32_t sl[2 << LR];    // selection byte of the row of word j (1 without a selection)
+    uint32_t ok = 0;         // bit j: word j belongs to a row of A.dst that is compared
+    uint32_t have[2 << LR];  // the caller's word j
+};
 
 // Decode: does this wave hold, after the FFT's remap, any row of A.dst (TWO: or of d2)?
 // (there the wave's rows are one block of 2^IW consecutive rows)
@@ -1018,6 +1030,59 @@ __device__ __forceinline__ void reveal_issue(const MonoCore &A, const uint32_t *
     });
 }
 
+// Verify: the words store_col would store are compared with the caller's instead.
+// Their loads go out in the prologue, behind the row and table loads, and land
+// while the transforms run: at the end of the kernel nothing would hide their
+// latency (a store needs no reply, a load does).  Measured, 64 stripes of 1024:1024
+// x 1 KiB per call: 253 us with the loads in store_col, 251 us with them at the end
+// of phase 1 (beside the requests for phase 3's tables), 240 us here; the batch
+// encode 224 us.  verify_select requests the selection bytes of the lane's rows
+// first of all (a call with a mask), so that verify_issue's wait for them leaves
+// everything issued in between in flight.
+// Every lane issues one load per word: a lane whose row is outside A.dst or not
+// selected reads row A.dst.row_begin (selected by contract: the host narrows the
+// map to the selected span) and discards it -- no branch around the loads (see
+// issue_col), and an unselected row is never read.
+template <int L, int LR, int SPLIT>
+__device__ __forceinline__ void verify_select(const MonoCore &A, VerifyPre<LR> &vp, uint32_t lane, uint32_t wave) {
+    using S = SeqOf<L, LR, true, SPLIT>;
+    constexpr int I = S::v.count;
+    const uint32_t span = A.dst.row_end - A.dst.row_begin;
+    const uint32_t i0 = paired_row<S, I, LR>(lane, wave, 0) - A.dst.row_begin;
+    static_for<0, (2 << LR)>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        vp.sl[j] = 1;
+    });
+    if (vp.sel) {  // (uniform)
+        static_for<0, (2 << LR)>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            const uint32_t idx = i0 + paired_delta<S, I, LR>(j);
+            vp.sl[j] = vp.sel[idx < span ? idx : 0u];
+        });
+    }
+}
+template <int L, int LR, int SPLIT, int E>
+__device__ __forceinline__ void verify_issue(const MonoCore &A, const PackIO &io, const StripeBases &sb,
+                                             VerifyPre<LR> &vp, uint32_t lane, uint32_t wave) {
+    using S = SeqOf<L, LR, true, SPLIT>;
+    constexpr int I = S::v.count;
+    const uint32_t span = A.dst.row_end - A.dst.row_begin;
+    const uint32_t off = io.lo + ((lane & 1u) ? io.hi_delta : 0u);
+    const uint32_t r0 = paired_row<S, I, LR>(lane, wave, 0);
+    const uint8_t *const p0 = map_base(A.dst, sb.dst, r0);  // (see row_at)
+    vp.ok = 0;
+    static_for<0, (2 << LR)>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        constexpr uint32_t D = paired_delta<S, I, LR>(j);
+        const bool ok = r0 + D - A.dst.row_begin < span && vp.sl[j] != 0;
+        vp.ok |= uint32_t(ok) << j;
+        const uint8_t *p = ok ? p0 + uint64_t(D) * A.dst.stride : sb.dst;
+        if constexpr (E == 2) vp.have[j] = ld_half(p + off, io);
+        else vp.have[j] = ld_word(p + off, io);
+    });
+    asm volatile("" ::: "memory");  // issued here, not next to the compare
+}
+
 // Store transform rows `chunk * n + row` that fall in A.dst (placement: end
 // of the FFT), paired like the loads.  REVEAL (decode): only erased rows,
 // multiplied by exp(65535 - log factor) (rate_high.rs:241-245); rt: tables
@@ -1025,11 +1090,15 @@ __device__ __forceinline__ void reveal_issue(const MonoCore &A, const uint32_t *
 // (AT_IFFT: rows in the placement at the end of the IFFT -- the half-split
 // kernels' work rows, kMonoHalfI)
 // (TWO: a repair's second map d2 -- a row goes to the map that holds it)
-template <int L, int LR, bool REVEAL, int SPLIT = 0, int E = 4, bool AT_IFFT = false, bool TWO = false>
+// (VERIFY: nothing is stored to A.dst -- the caller's word at the address of each
+// store, loaded by verify_issue, is compared with the finished word, and a
+// difference sets the row's flag, vp)
+template <int L, int LR, bool REVEAL, int SPLIT = 0, int E = 4, bool AT_IFFT = false, bool TWO = false,
+          bool VERIFY = false>
 __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *rowinfo, uint32_t chunk,
                                           const PackIO &io, const StripeBases &sb, Col<L, LR, E> &c, uint32_t lane,
                                           uint32_t wave, const RevealTabs<LR> *rt = nullptr,
-                                          const Dst2 &d2 = Dst2{}) {
+                                          const Dst2 &d2 = Dst2{}, const VerifyPre<LR> *vp = nullptr) {
     using S = SeqOf<L, LR, !AT_IFFT, SPLIT>;
     constexpr uint32_t PC = Fmt<E>::kPC;
     constexpr int I = S::v.count;
@@ -1077,6 +1146,18 @@ __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *row
     uint8_t *const p0 = const_cast<uint8_t *>(map_base(A.dst, sb.dst, r0));  // (see row_at)
     uint8_t *q0 = nullptr;
     if constexpr (TWO) q0 = const_cast<uint8_t *>(map_base(d2.m, d2.base, r0));
+    if constexpr (VERIFY) {
+        static_assert(!REVEAL && !TWO && !AT_IFFT, "verify: the encode's store");
+        // the bytes that exist: a byte-wise pack of fewer elements loaded io.cnt bytes
+        constexpr uint32_t kFull = E == 2 ? 0xFFFFu : 0xFFFFFFFFu;
+        const uint32_t m = io.bytes && io.cnt < uint32_t(E) ? (1u << (8u * io.cnt)) - 1u : kFull;
+        static_for<0, 2 * R>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (((vp->ok >> j) & 1u) && vp->have[j] != (w[j] & m))
+                vp->flags[r0 + paired_delta<S, I, LR>(j) - A.dst.row_begin] = 1;
+        });
+        return;
+    }
     static_for<0, 2 * R>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         constexpr uint32_t D = paired_delta<S, I, LR>(j);
@@ -1789,9 +1870,13 @@ using MonoArgM = std::conditional_t<MASKS, MonoMaskArgs, MonoArgT<MODE, STAGED>>
 
 // TWO (k_mono_repair): the decode with a second destination map (KA = MonoArgs2;
 // with MASKS, k_mono_repair_masks: KA = MonoMaskArgs2)
+// VERIFY (k_mono_verify, rs_verify.hip): the staged encode whose store_col compares
+// with the caller's rows and sets flags instead of storing (KA = MonoVerifyArgs)
 template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, bool MASKS = false, bool TWO = false,
-          typename KA = MonoArgM<MODE, STAGED, MASKS>>
+          bool VERIFY = false, typename KA = MonoArgM<MODE, STAGED, MASKS>>
 __device__ __forceinline__ void mono_body(const KA &K) {
+    static_assert(!VERIFY || (STAGED && !MASKS && !TWO && (MODE == kMonoEncodeHigh || MODE == kMonoEncodeLow)),
+                  "verify: the staged single-chunk encode");
     // (MASKS and TWO together, k_mono_repair_masks: MASKS' own conditions below hold)
     static_assert(!TWO || MODE == kMonoDecode || (!MASKS && MODE == kMonoHalfFDec), "second destination: decodes");
     static_assert(!MASKS || (MODE == kMonoDecode && STAGED && BATCH && !SPLIT),
@@ -1916,6 +2001,11 @@ __device__ __forceinline__ void mono_body(const KA &K) {
     if constexpr (TWO) {
         d2.m = K.dst2;
         d2.base = const_cast<uint8_t *>(K.dst2.base) + (BATCH ? uint64_t(blockIdx.y) * K.dst2_bstride : 0);
+    }
+    VerifyPre<LR> vp;
+    if constexpr (VERIFY) {
+        vp.flags = K.flags + (BATCH ? uint64_t(blockIdx.y) * K.flag_bstride : 0);
+        vp.sel = K.sel;
     }
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2147,11 +2237,13 @@ __device__ __forceinline__ void mono_body(const KA &K) {
                 issue_priv();
                 issue_shared();
             } else if constexpr (!DEC) {
+                if constexpr (VERIFY) verify_select<L, LR, PK>(A, vp, lane, wave);
                 if constexpr (QUAD) issue_quad<L, LR, PK>(A, io, sb, wq, okmq, lane, wave);
                 else issue_rows(kIO{});
                 issue_priv();
                 issue_shared();
                 issue_quad_tabs();
+                if constexpr (VERIFY) verify_issue<L, LR, PK, E>(A, io, sb, vp, lane, wave);
             } else {
                 if constexpr (kShFirst) issue_shared();
                 RS_MSTAMP(16);
@@ -2417,8 +2509,8 @@ __device__ __forceinline__ void mono_body(const KA &K) {
                 quad_layer0<L, LR, SQ, SQ::v.count, true>(c, qtab + QW * kQuad0Slot, lane, wave);  // FFT layer 0
                 store_quad<L, LR, PK>(A, io, sb, c, lane, wave);
             } else {
-                store_col<L, LR, DEC || HFD, PK, E, false, TWO>(A, ri, HALF_F ? hh : 0u, io, sb, c, lane, wave,
-                                                                kPreReveal && G::WB > 0 ? &rt : nullptr, d2);
+                store_col<L, LR, DEC || HFD, PK, E, false, TWO, VERIFY>(A, ri, HALF_F ? hh : 0u, io, sb, c, lane, wave,
+                                                                        kPreReveal && G::WB > 0 ? &rt : nullptr, d2, &vp);
             }
             RS_MSTAMP(11);
       };
@@ -2703,7 +2795,62 @@ hipError_t launch_mono_repair_masks(int L, const MonoMaskArgs2 &A, hipStream_t s
     }
 }
 
-#else  // !RS_MONO_REPAIR_TU
+#elif defined(RS_MONO_VERIFY_TU)
+// rs_verify.hip: this file's kernel body compiled once more, as a translation unit
+// that holds only the verify instantiations (VERIFY: store_col compares instead of
+// storing, rs_device.hpp MonoVerifyArgs).  The encode's kernels are not part of it
+// and this file's own object holds none of these.
+namespace {
+
+// always the batch form (one stripe: grid.y = 1) and one kernel for both rates:
+// the staged body of kMonoEncodeHigh and kMonoEncodeLow is the same code
+template <int L, int E>
+__global__ void __launch_bounds__(1 << (L - 1)) k_mono_verify(const MonoVerifyArgs A) {
+    mono_body<L, 1, kMonoEncodeHigh, true, true, false, E, false, false, true>(A);
+}
+
+template <int L, int E>
+hipError_t launch_verify_le(const MonoVerifyArgs &A, hipStream_t s) {
+    constexpr int LR = mono_lr(L, true);
+    static_assert(LR == 1, "k_mono_verify: 2 rows per lane");
+    using G = Stage<L, LR, mono_pk(kMonoEncodeHigh, true, false), E>;
+    size_t lds = size_t(G::words_enc) * 4;
+    if (E == 2 && lds <= 80 * 1024) lds = 84 * 1024;  // (as launch_ls)
+    static std::atomic<uint64_t> attr_devs{0};
+    if (lds > 65536) {
+        hipError_t e = lds_attr_once(attr_devs, reinterpret_cast<const void *>(&k_mono_verify<L, E>), int(lds));
+        if (e != hipSuccess) return e;
+    }
+    k_mono_verify<L, E><<<dim3(8u * A.packs_per_xcd, A.stripes), 1 << (L - LR), lds, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono_verify<%d, %d>", L, E);
+    return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_verify_l(const MonoVerifyArgs &A, hipStream_t s) {
+    if constexpr (!(RS_MONO_HAS_L(L) && RS_MONO_HAS_MODE(kMonoEncodeHigh) && staged_l(L))) {
+        return hipErrorNotSupported;
+    } else {
+        return A.elems == 2 ? launch_verify_le<L, 2>(A, s) : launch_verify_le<L, 4>(A, s);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_mono_verify(int L, const MonoVerifyArgs &A, hipStream_t s) {
+    if (A.packs == 0 || A.stripes == 0 || A.dst.row_end <= A.dst.row_begin) return hipSuccess;
+    if (!A.flags || A.chunks != 1 || A.stripes > 65535 || (A.elems != 2 && A.elems != 4)) return hipErrorInvalidValue;
+    switch (L) {
+        case 7: return launch_verify_l<7>(A, s);
+        case 8: return launch_verify_l<8>(A, s);
+        case 9: return launch_verify_l<9>(A, s);
+        case 10: return launch_verify_l<10>(A, s);
+        case 11: return launch_verify_l<11>(A, s);
+        default: return hipErrorNotSupported;
+    }
+}
+
+#else  // the file's own object
 
 hipError_t launch_mono_half(int mode, uint32_t halves, const MonoArgs &A, hipStream_t s) {
     if (A.packs == 0 || halves == 0) return hipSuccess;
@@ -2842,6 +2989,6 @@ hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t s) {
     }
 }
 
-#endif  // RS_MONO_REPAIR_TU
+#endif  // RS_MONO_REPAIR_TU / RS_MONO_VERIFY_TU
 
 }  // namespace rs

@@ -116,6 +116,10 @@ _sig("rs_update_device", _int, _vp, _int, _u64, _u64, _u64, ctypes.POINTER(_u64)
 _sig("rs_update_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, ctypes.POINTER(_u64), _u64, _vp, _u64, _u64, _vp,
      _u64, _u64, _vp, _u64, _u64, ctypes.c_char_p, _vp, _E)
 _sig("rs_update_set_direct_max", _int, _vp, ctypes.c_uint32)
+_sig("rs_verify_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, _vp, _vp, _E)
+_sig("rs_verify_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     ctypes.c_char_p, _vp, _vp, _E)
+_sig("rs_verify_set_fused", _int, _vp, _int)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -1058,6 +1062,81 @@ def update_set_direct_max(k: int, ctx: Optional[Context] = None) -> None:
     stripe is re-encoded (rs_update_set_direct_max; 0 = always re-encode)."""
     ctx = ctx or default_context()
     if _lib.rs_update_set_direct_max(ctx.handle, int(k)) != 0:
+        raise ValueError("invalid argument (rs_status 101)")
+
+
+VERIFY_FUSED_DEFAULT = 1  # RS_VERIFY_FUSED_DEFAULT (include/rs_mi355x.h)
+
+
+def _check_flags(d_mismatch, shape, like):
+    """The flag tensor of a verify: the caller's (uint8, on the device, contiguous, exactly `shape`:
+    the library writes shape-product bytes, densely) or a new one on the device of `like`."""
+    if d_mismatch is None:
+        if not hasattr(like, "data_ptr"):
+            raise ValueError("d_mismatch: needed when the matrices are raw pointers")
+        import torch
+        return torch.empty(shape, dtype=torch.uint8, device=like.device)
+    if hasattr(d_mismatch, "data_ptr"):
+        if str(d_mismatch.dtype) != "torch.uint8":
+            raise ValueError(f"d_mismatch: dtype must be uint8, got {d_mismatch.dtype}")
+        if not d_mismatch.is_cuda:
+            raise ValueError("d_mismatch: must be a device (cuda/HIP) tensor")
+        if tuple(d_mismatch.shape) != tuple(shape) or not d_mismatch.is_contiguous():
+            raise ValueError(f"d_mismatch: expected a contiguous tensor of shape {tuple(shape)}, "
+                             f"got {tuple(d_mismatch.shape)}")
+    return d_mismatch
+
+
+def verify_device(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                  recovery_rows=None, d_mismatch=None, stream=None, rate_: int = RATE_DEFAULT,
+                  ctx: Optional[Context] = None):
+    """Check the recovery shards against the originals (rs_verify_device).  Returns the uint8 flag
+    tensor [recovery_count] (d_mismatch, or a new one on the inputs' device): 1 = that recovery
+    shard differs from what encode_device would produce, 0 = it matches or was not selected.
+    recovery_rows: recovery_count flags, 0 = do not check (and never read) that row; None = every
+    row.  Nothing but the flags is written.  Asynchronous on `stream`."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
+                                                          "recovery_rows")
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_verify_device(ctx.handle, rate_, original_count, recovery_count, shard_bytes, _ptr(d_original),
+                                 _row_stride(d_original), _ptr(d_recovery), _row_stride(d_recovery), rows,
+                                 _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
+    return d_mismatch
+
+
+def verify_device_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                        recovery_rows=None, d_mismatch=None, stream=None, rate_: int = RATE_DEFAULT,
+                        ctx: Optional[Context] = None):
+    """verify_device on a batch of stripes sharing ONE row mask (rs_verify_device_batch); tensors
+    [stripes, rows, shard_bytes].  Returns the flag tensor [stripes, recovery_count]."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
+                                                          "recovery_rows")
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_verify_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                       d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows,
+                                       _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
+    return d_mismatch
+
+
+def verify_set_fused(mode: int, ctx: Optional[Context] = None) -> None:
+    """0: verify_device always encodes into scratch and compares; 1: the fused column kernel
+    where the shape has one (rs_verify_set_fused)."""
+    ctx = ctx or default_context()
+    if _lib.rs_verify_set_fused(ctx.handle, int(mode)) != 0:
         raise ValueError("invalid argument (rs_status 101)")
 
 
