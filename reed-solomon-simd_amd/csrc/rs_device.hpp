@@ -286,6 +286,22 @@ struct MonoCore {
     uint32_t half0 = 0, zero_halves = 0;
     const uint32_t *top_i = nullptr, *top_f = nullptr;
 };
+// The staged single-chunk encodes take the fields their prologue needs as plain
+// leading kernel parameters, 14 dwords in this order (no padding), followed by the
+// MonoCore: gfx950 preloads argument dwords into the user SGPRs at wave launch, plain
+// parameters only, and 14 are free beside the argument pointer (rs_mono.hip k_mono's
+// encode entry).  The first two lines let the row loads go (one source map: nsrc = 1),
+// the third the table loads.
+struct MonoLead {
+    const uint8_t *src;
+    uint64_t src_stride;
+    uint32_t src_begin, src_end, packs, packs_per_xcd, full_packs;
+    uint32_t tail_io;  // ShardFormat: tail_h | io_bytes << 16
+    const uint32_t *img;
+    uint32_t img_words;
+    uint32_t imgs;  // ifft_img | fft_img << 16
+};
+static_assert(sizeof(MonoLead) == 56, "14 dwords, no padding");
 struct MonoArgs : MonoCore {
     // fused-eval_poly decode: erased / received bits of the 2^L work rows, as in EvalArgs
     uint32_t erased[kMonoFusedRows / 32] = {}, received[kMonoFusedRows / 32] = {};

@@ -335,6 +335,18 @@ struct GlobalTabs {
 // RS_MONO_BASIS (rs_device.hpp) is off: 1 builds k_mono with it (the host then
 // hands it basis images, rs_codec.cpp mono_args).
 
+// Encodes skip the barrier that opens a remap where the remap's column plane has no
+// earlier reader or writer in the workgroup: remap 1 (nothing touches the plane
+// before it) and remap 2 once it has a plane of its own (Stage::kPlane2).  0 keeps
+// both barriers and the single plane.  Measured no faster, so 0: the headline encode
+// 7.92-7.98 us per launch with all four barriers, 7.92-7.96 with two, and beside the
+// preloaded arguments 7.28-7.31 against 7.31-7.35 (profiles/r08a/probe_ab.txt, 4
+// alternating rounds): the barrier between a remap's writes and reads already waits
+// for the slowest wave, the opening one then finds every wave there.
+#ifndef RS_MONO_SPARE_BARRIERS
+#define RS_MONO_SPARE_BARRIERS 0
+#endif
+
 template <int L, int LR, int SP = 0, int E = 4>
 struct Stage {
     static constexpr bool SPLIT = Plan<L, LR, SP>::SPLIT;
@@ -432,10 +444,16 @@ struct Stage {
 #endif
     static constexpr uint32_t kD = kDerive3 ? NB3 : 0;
     static constexpr uint32_t words_enc = words + kD * SW;
+    // encodes (kMonoEncodeHigh / Low, verify): + a second column plane for the FFT's
+    // remap, where it fits, so that neither remap of an encode has earlier readers
+    // of its plane to wait for (apply_remap IDLE, RS_MONO_SPARE_BARRIERS).  The
+    // half-split and quad kernels keep words_enc
+    static constexpr bool kPlane2 = RS_MONO_SPARE_BARRIERS && WB > 0 && (words_enc + plane_words) * 4 <= 160 * 1024;
+    static constexpr uint32_t words_enc2 = words_enc + (kPlane2 ? plane_words : 0);
     static constexpr uint32_t words_dec = words + n;  // + per-row decode info (fused eval_poly)
     // SPLIT decode: + a second column plane (the cross-half step's formal-derivative values)
     static constexpr uint32_t words_split = words_dec + (SPLIT ? plane_words : 0);
-    static_assert(L > 11 || (words_enc * 4 <= 160 * 1024 && words_split * 4 <= 160 * 1024), "column kernel: LDS per workgroup");
+    static_assert(L > 11 || (words_enc2 * 4 <= 160 * 1024 && words_split * 4 <= 160 * 1024), "column kernel: LDS per workgroup");
 };
 
 // Table source: tables staged in LDS (STAGED column kernel).  Phase 1 (IFFT
@@ -547,10 +565,12 @@ __device__ __forceinline__ void apply_xpose(Col<L, LR, E> &c, uint32_t lane) {
 }
 
 // Whole-column exchange through LDS from placement maps[I] to maps[I + 1].
-template <int L, int LR, typename S, int I, int E>
+// IDLE: no wave of the workgroup has read or written `plane` before this remap, so
+// the barrier that waits for the plane's earlier readers is left out.
+template <int L, int LR, typename S, int I, int E, bool IDLE = false>
 __device__ __forceinline__ void apply_remap(Col<L, LR, E> &c, uint32_t *plane, uint32_t lane, uint32_t wave) {
     constexpr uint32_t n = 1u << L;
-    __syncthreads();
+    if constexpr (!IDLE) __syncthreads();
     const uint32_t a = lane_rows<S, I>(lane, wave);
     static_for<0, (1 << LR)>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
@@ -658,11 +678,12 @@ struct NoHook {
 // the ops after it.  zero_top: the transform's skew offset is 0 (image 0), so
 // the single twiddle of its top layer L-1 is skew[2^(L-1) - 1] = GF_MODULUS
 // (tables.rs:285-324: the 16 such entries are skew[2^b - 1]), a multiply-free layer.
+// Idle (std::true_type): the remap finds `plane` untouched (apply_remap IDLE).
 template <int L, int LR, bool FFT, int B0, int KHOOK = -1, int SPLIT = 0, typename TS, typename PreRemap,
-          int E, typename Hook = NoHook>
+          int E, typename Hook = NoHook, typename Idle = std::false_type>
 __device__ __forceinline__ void run_seq(const TS &ts, Col<L, LR, E> &c, uint32_t *plane, uint32_t lane, uint32_t wave,
                                         const PreRemap &pre_remap, bool alive = true, bool pre = true,
-                                        const Hook &hook = Hook{}, bool zero_top = false) {
+                                        const Hook &hook = Hook{}, bool zero_top = false, Idle = Idle{}) {
     using S = SeqOf<L, LR, FFT, SPLIT>;
     constexpr int NT = (1 << LR) / 2;
     constexpr int NL = num_layers(S::v);
@@ -692,7 +713,7 @@ __device__ __forceinline__ void run_seq(const TS &ts, Col<L, LR, E> &c, uint32_t
             pre_remap();
             RS_MSTAMP(FFT ? 8 : 3);
 #ifndef RS_MONO_SKIP_REMAP  // tools/mono_probe.hip ablation
-            apply_remap<L, LR, S, I, E>(c, plane, lane, wave);
+            apply_remap<L, LR, S, I, E, Idle::value>(c, plane, lane, wave);
 #endif
             RS_MSTAMP(FFT ? 9 : 4);
             if (alive) prime(std::integral_constant<int, NL1>{}, std::integral_constant<int, NL>{});
@@ -1872,9 +1893,18 @@ using MonoArgM = std::conditional_t<MASKS, MonoMaskArgs, MonoArgT<MODE, STAGED>>
 // with MASKS, k_mono_repair_masks: KA = MonoMaskArgs2)
 // VERIFY (k_mono_verify, rs_verify.hip): the staged encode whose store_col compares
 // with the caller's rows and sets flags instead of storing (KA = MonoVerifyArgs)
+// PRE (k_mono's encode entry, RS_MONO_PRELOAD): K was put together by the kernel entry
+// from plain leading parameters, which arrive in SGPRs with the wave (kernel-argument
+// preload), and the rest of MonoCore, which is loaded from the argument segment.
+// Everything the prologue's row and table loads need is in the first group; the
+// destination map, the only other thing an encode reads, is waited for after
+// those loads are issued (pin_rest).
 template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, bool MASKS = false, bool TWO = false,
-          bool VERIFY = false, typename KA = MonoArgM<MODE, STAGED, MASKS>>
-__device__ __forceinline__ void mono_body(const KA &K) {
+          bool VERIFY = false, bool PRE = false, typename KA = MonoArgM<MODE, STAGED, MASKS>>
+__device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const MonoLead *lead = nullptr) {
+    static_assert(!PRE || (STAGED && !SPLIT && !MASKS && !TWO && !VERIFY &&
+                           (MODE == kMonoEncodeHigh || MODE == kMonoEncodeLow)),
+                  "preloaded arguments: the staged single-chunk encode");
     static_assert(!VERIFY || (STAGED && !MASKS && !TWO && (MODE == kMonoEncodeHigh || MODE == kMonoEncodeLow)),
                   "verify: the staged single-chunk encode");
     // (MASKS and TWO together, k_mono_repair_masks: MASKS' own conditions below hold)
@@ -1884,7 +1914,19 @@ __device__ __forceinline__ void mono_body(const KA &K) {
     MonoCore A;  // the scalar arguments; the erasure bitmaps stay in K
     uint32_t ew[4] = {0, 0, 0, 0}, rw[4] = {0, 0, 0, 0};  // staged decode: the wave's bitmap words
     uint32_t skip_stripe = 0;  // MASKS: the stripe's descriptor says skip
-    {
+    if constexpr (PRE) {  // (nothing to wait for here: see pin_rest)
+        A.packs = lead->packs;
+        A.packs_per_xcd = lead->packs_per_xcd;
+        A.nsrc = 1;
+        A.src[0] = RowMap{lead->src, lead->src_stride, lead->src_begin, lead->src_end};
+        A.src[1] = A.src[0];  // (never read as a second map: nsrc = 1)
+        A.dst = K.dst;
+        A.img = lead->img;
+        A.img_words = lead->img_words;
+        A.ifft_img = lead->imgs & 0xFFFFu;
+        A.fft_img = lead->imgs >> 16;
+        A.fmt = ShardFormat{lead->full_packs, lead->tail_io & 0xFFFFu, lead->tail_io >> 16};
+    } else {
         uint32_t packs = K.packs, ppx = K.packs_per_xcd, nsrc = K.nsrc;
         gptr<const uint8_t> b0 = as_global(K.src[0].base), b1 = as_global(K.src[1].base);
         gptr<const uint8_t> bd = as_global(K.dst.base);
@@ -1992,7 +2034,7 @@ __device__ __forceinline__ void mono_body(const KA &K) {
     const uint32_t b = blockIdx.x;
     const uint32_t pk = (b & 7u) * A.packs_per_xcd + (b >> 3);
     if (pk >= A.packs) return;
-    const StripeBases sb = BATCH ? stripe_bases(A, blockIdx.y) : StripeBases{A.src[0].base, A.src[1].base,
+    StripeBases sb = BATCH ? stripe_bases(A, blockIdx.y) : StripeBases{A.src[0].base, A.src[1].base,
                                                                              const_cast<uint8_t *>(A.dst.base)};
     // the pack's bytes in the caller's rows (tails: shards.rs:38-74)
     // (quad encode: 2-element column packs, computed as 4-element pair-row packs)
@@ -2244,6 +2286,19 @@ __device__ __forceinline__ void mono_body(const KA &K) {
                 issue_shared();
                 issue_quad_tabs();
                 if constexpr (VERIFY) verify_issue<L, LR, PK, E>(A, io, sb, vp, lane, wave);
+                if constexpr (PRE) {
+                    // pin_rest: the destination map comes from the argument segment (the
+                    // other arguments an encode reads arrived in SGPRs).  Its scalar loads
+                    // are waited for here, behind the row and table loads, and the values
+                    // pinned so that the stores at the end do not load them again
+                    gptr<const uint8_t> bd = as_global(A.dst.base);
+                    gptr<uint8_t> sd = as_global(sb.dst);
+                    uint64_t std_ = A.dst.stride;
+                    uint32_t rbd = A.dst.row_begin, red = A.dst.row_end;
+                    asm volatile("" : "+s"(bd), "+s"(sd), "+s"(std_), "+s"(rbd), "+s"(red));
+                    A.dst = RowMap{(const uint8_t *)bd, std_, rbd, red};
+                    sb.dst = (uint8_t *)sd;
+                }
             } else {
                 if constexpr (kShFirst) issue_shared();
                 RS_MSTAMP(16);
@@ -2477,8 +2532,16 @@ __device__ __forceinline__ void mono_body(const KA &K) {
                                                                                 alive, true, write4, fi == 0);
                 if (!alive) return;
             } else if constexpr (G::WB > 0) {
+                // encodes: no wave touches the column plane before remap 1, and remap 2
+                // gets a plane of its own where it fits (Stage::kPlane2): their opening
+                // barriers are left out, an encode keeps the two between a remap's
+                // writes and reads (remap 1's also orders the shared region's writes)
+                constexpr bool kEnc = MODE == kMonoEncodeHigh || MODE == kMonoEncodeLow;
+                using Idle1 = std::bool_constant<kEnc && RS_MONO_SPARE_BARRIERS>;
+                using Idle2 = std::bool_constant<kEnc && G::kPlane2>;
+                uint32_t *const plane_f = Idle2::value ? lds + G::words_enc : plane;
                 run_seq<L, LR, false, RS_MONO_LDS_PF, G::B0 ? 1 : -1, PK>(ts, c, plane, lane, wave, issue3, true, live,
-                                                                       write1, ii == 0);
+                                                                       write1, ii == 0, Idle1{});
                 if constexpr (HALF_I) {  // the half's IFFT rows to the work rows; no FFT here
                     store_col<L, LR, false, PK, E, true>(A, ri, hh, io_w, sb, c, lane, wave);
                     RS_MSTAMP(11);
@@ -2490,8 +2553,8 @@ __device__ __forceinline__ void mono_body(const KA &K) {
                 const bool alive = !DEC || wave_stores<L, LR, PK, TWO>(A, wave, 0, d2);
                 issue4(alive);  // (waves that stop early all read one table: no branch around the loads)
                 if constexpr (DEC) formal_derivative<L, LR>(c, plane, lane, wave);
-                run_seq<L, LR, true, RS_MONO_LDS_PF, G::B0 ? NLF - 1 : -1, PK>(ts, c, plane, lane, wave, pre3(alive), alive,
-                                                                            true, write4, fi == 0);
+                run_seq<L, LR, true, RS_MONO_LDS_PF, G::B0 ? NLF - 1 : -1, PK>(ts, c, plane_f, lane, wave, pre3(alive), alive,
+                                                                            true, write4, fi == 0, Idle2{});
                 if (!alive) return;
             } else {
                 static_assert(!G::B0, "one-segment plans keep every table in the region");
@@ -2560,6 +2623,33 @@ template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E>
 __global__ void __launch_bounds__(1 << (L - LR)) k_mono(const MonoArgT<MODE, STAGED> A) {
     mono_body<L, LR, MODE, STAGED, BATCH, SPLIT, E>(A);
 }
+// The staged single-chunk encodes' entry (RS_MONO_PRELOAD, default 1; 0: the entry
+// above): the first 14 dwords of the arguments are plain parameters (rs_device.hpp
+// MonoLead), which gfx950 hands to every wave in SGPRs at launch (kernel-argument
+// preload; this file is built with -mllvm -amdgpu-kernarg-preload-count=14, the
+// user SGPRs left beside the argument pointer, and the compiler keeps a loading
+// prologue for firmware that does not preload), in the order the prologue needs
+// them: the source rows, the pack counts and the shard format let the row loads go,
+// the image pointer, words and indices the table loads.  R: the other arguments as
+// before (of its fields named above only the values here are read; an encode has
+// one source map).  The same name and template arguments as the entry
+// above, so the kernel keeps its name in traces; the return type keeps this overload
+// out of every other mode's overload set.
+#ifndef RS_MONO_PRELOAD
+#define RS_MONO_PRELOAD 1
+#endif
+constexpr bool mono_pre(int mode, bool staged, bool split) {
+    return RS_MONO_PRELOAD && staged && !split && (mode == kMonoEncodeHigh || mode == kMonoEncodeLow);
+}
+template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E>
+__global__ std::enable_if_t<mono_pre(MODE, STAGED, SPLIT)> __launch_bounds__(1 << (L - LR))
+k_mono(const uint8_t *src, uint64_t src_stride, uint32_t src_begin, uint32_t src_end, uint32_t packs,
+       uint32_t packs_per_xcd, uint32_t full_packs, uint32_t tail_io, const uint32_t *img, uint32_t img_words,
+       uint32_t imgs, const MonoCore R) {
+    const MonoLead lead{src, src_stride, src_begin, src_end, packs, packs_per_xcd, full_packs, tail_io, img, img_words,
+                        imgs};
+    mono_body<L, LR, MODE, STAGED, BATCH, SPLIT, E, false, false, false, true>(R, &lead);
+}
 #ifndef RS_MONO_LR10
 #define RS_MONO_LR10 1
 #endif
@@ -2581,20 +2671,37 @@ template <int L, int MODE, bool STAGED, bool BATCH = false, bool SPLIT = false, 
 hipError_t launch_ls(const MonoArgs &A, hipStream_t s) {
     constexpr int LR = mono_lr(L, STAGED);
     using G = Stage<L, LR, mono_pk(MODE, STAGED, SPLIT), E>;
-    size_t lds = STAGED ? size_t(SPLIT ? G::words_split : MODE == kMonoDecode ? G::words_dec : G::words_enc) * 4
+    size_t lds = STAGED ? size_t(SPLIT ? G::words_split : MODE == kMonoDecode ? G::words_dec : G::words_enc2) * 4
                         : size_t(8) << L;
     // 2-element packs exist to spread a launch over more CUs: more than half the
     // CU's LDS keeps the dispatcher from doubling workgroups up on one CU
     if (E == 2 && lds <= 80 * 1024) lds = 84 * 1024;
     static std::atomic<uint64_t> attr_devs{0};  // devices whose attribute is set
-    if (lds > 65536) {
-        hipError_t e = lds_attr_once(
-            attr_devs, reinterpret_cast<const void *>(&k_mono<L, LR, MODE, STAGED, BATCH, SPLIT, E>), int(lds));
-        if (e != hipSuccess) return e;
-    }
     const uint32_t grid = 8u * A.packs_per_xcd;
-    k_mono<L, LR, MODE, STAGED, BATCH, SPLIT, E>
-        <<<dim3(grid, BATCH ? A.stripes : 1), 1 << (L - LR), lds, s>>>(static_cast<const MonoArgT<MODE, STAGED> &>(A));
+    if constexpr (mono_pre(MODE, STAGED, SPLIT)) {  // the entry with preloaded leading arguments
+        if (A.nsrc != 1 || A.img_words > 0xFFFFFFFFull || A.fmt.tail_h > 0xFFFFu || A.ifft_img > 0xFFFFu ||
+            A.fft_img > 0xFFFFu)
+            return hipErrorInvalidValue;
+        using Fn = void (*)(const uint8_t *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
+                            const uint32_t *, uint32_t, uint32_t, const MonoCore);
+        const Fn fn = &k_mono<L, LR, MODE, STAGED, BATCH, SPLIT, E>;
+        if (lds > 65536) {
+            hipError_t e = lds_attr_once(attr_devs, reinterpret_cast<const void *>(fn), int(lds));
+            if (e != hipSuccess) return e;
+        }
+        fn<<<dim3(grid, BATCH ? A.stripes : 1), 1 << (L - LR), lds, s>>>(
+            A.src[0].base, A.src[0].stride, A.src[0].row_begin, A.src[0].row_end, A.packs, A.packs_per_xcd,
+            A.fmt.full_packs, A.fmt.tail_h | uint32_t(A.fmt.io_bytes != 0) << 16, A.img, uint32_t(A.img_words),
+            A.ifft_img | A.fft_img << 16, static_cast<const MonoCore &>(A));
+    } else {
+        if (lds > 65536) {
+            hipError_t e = lds_attr_once(
+                attr_devs, reinterpret_cast<const void *>(&k_mono<L, LR, MODE, STAGED, BATCH, SPLIT, E>), int(lds));
+            if (e != hipSuccess) return e;
+        }
+        k_mono<L, LR, MODE, STAGED, BATCH, SPLIT, E><<<dim3(grid, BATCH ? A.stripes : 1), 1 << (L - LR), lds, s>>>(
+            static_cast<const MonoArgT<MODE, STAGED> &>(A));
+    }
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono<%d, %d, %d, %s, %s, %s, %d>", L, LR, MODE,
              STAGED ? "true" : "false", BATCH ? "true" : "false", SPLIT ? "true" : "false", E);
     return hipGetLastError();
@@ -2814,7 +2921,7 @@ hipError_t launch_verify_le(const MonoVerifyArgs &A, hipStream_t s) {
     constexpr int LR = mono_lr(L, true);
     static_assert(LR == 1, "k_mono_verify: 2 rows per lane");
     using G = Stage<L, LR, mono_pk(kMonoEncodeHigh, true, false), E>;
-    size_t lds = size_t(G::words_enc) * 4;
+    size_t lds = size_t(G::words_enc2) * 4;
     if (E == 2 && lds <= 80 * 1024) lds = 84 * 1024;  // (as launch_ls)
     static std::atomic<uint64_t> attr_devs{0};
     if (lds > 65536) {
