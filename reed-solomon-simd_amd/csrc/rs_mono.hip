@@ -28,6 +28,7 @@
 
 #include "rs_device.hpp"
 #include "rs_gf.hpp"
+#include "rs_stage_map.hpp"
 
 namespace rs {
 namespace {
@@ -384,33 +385,17 @@ struct Stage {
     // 4-element encode's 106K -> 204K (the permuted staging writes and the phase-3 XOR
     // pass conflict instead) and +0.2 us, so only the 2-element format uses it
     static constexpr bool kGray = E == 2;
-    static __device__ __forceinline__ uint32_t sg(uint32_t g) { return kGray ? g ^ ((g >> 1) & 15u) : g; }
+    // (the maps themselves, forward and inverse: rs_stage_map.hpp, shared with the host test)
+    static __device__ __forceinline__ uint32_t sg(uint32_t g) { return SM::sg(g); }
     // slot of table t of a region sequence of 2^k - 1 tables, layers largest first
     // (layer of size 2^m starts at 2^k - 2^(m+1), a multiple of 2^m)
-    static __device__ __forceinline__ uint32_t sq(uint32_t t, uint32_t k) {
-        if constexpr (!kGray) return t;
-        const uint32_t y = (1u << k) - t;  // 2^m < y <= 2^(m+1)
-        const uint32_t mask = y <= 1u ? 0u : (1u << (31 - __builtin_clz(y - 1u))) - 1u;
-        return t ^ (((t & mask) >> 1) & 15u);
-    }
-    // LDS position (16-byte units) of piece q of table slot (q / PC) -> f(q / PC)
-    template <typename F>
-    static __device__ __forceinline__ uint32_t at(uint32_t q, F f) {
-        const uint32_t t = q / PC;
-        return f(t) * SPC + (q - t * PC);
-    }
+    static __device__ __forceinline__ uint32_t sq(uint32_t t, uint32_t k) { return SM::sq(t, k); }
+    // LDS position (16-byte units) of piece q of table slot (q / PC) -> f(q / PC):
     // the phase-1 / -3 region (layers B0..IW-1), its layer-0 turn (B0), the shared region
-    static __device__ __forceinline__ uint32_t at1(uint32_t q) {
-        return at(q, [](uint32_t t) { return sq(t, uint32_t(IW - B0)); });
-    }
-    static __device__ __forceinline__ uint32_t at0(uint32_t q) { return at(q, [](uint32_t t) { return sg(t); }); }
-    static __device__ __forceinline__ uint32_t atS(uint32_t q) {
-        return at(q, [](uint32_t t) {
-            if (t < kShI) return sq(t, uint32_t(L - IW));
-            if (t < kShI + kShF) return kShI + sq(t - kShI, uint32_t(L - FLO));
-            return t;  // D tables: one per layer
-        });
-    }
+    // (D tables: one per layer, after the shared tables in order)
+    static __device__ __forceinline__ uint32_t at1(uint32_t q) { return SM::at1(q); }
+    static __device__ __forceinline__ uint32_t at0(uint32_t q) { return SM::at0(q); }
+    static __device__ __forceinline__ uint32_t atS(uint32_t q) { return SM::atS(q); }
     static constexpr int IW = LR + 6, WB = L - IW - (SPLIT ? 1 : 0);
     static constexpr uint32_t n = 1u << L, W = 1u << IW;
     // layers of the last (FFT) in-wave phase
@@ -421,6 +406,7 @@ struct Stage {
 #define RS_MONO_B0_MIN_L 11
 #endif
     static constexpr int B0 = L >= RS_MONO_B0_MIN_L ? 1 : 0;
+    using SM = StageMap<L, LR + 6, FLO, B0, E>;
     // tables per wave region; with B0 the region first holds layer 0's W/2
     // tables, then (written over them, see run_seq's hook) the layers above
     static constexpr uint32_t kPriv = B0 ? (W >> 1) : W - 1;
@@ -430,6 +416,9 @@ struct Stage {
     static constexpr uint32_t kShI = WB > 0 ? (n >> IW) - 1 : 0;     // shared: IFFT layers IW..L-1
     static constexpr uint32_t kShF = WB > 0 ? (n >> FLO) - 1 : 0;    // shared: FFT layers FLO..L-1
     static constexpr uint32_t kShared = kShI + kShF;
+    static_assert(SM::PC == PC && SM::SPC == SPC && SM::kUp == kUp && SM::kP3 == kP3 && SM::kL0 == kL0 &&
+                      SM::kPriv == kPriv && SM::kShI == kShI && SM::kShF == kShF,
+                  "rs_stage_map.hpp: the same regions");
     static constexpr uint32_t kWaves = 1u << (L - LR - 6);
     static constexpr uint32_t plane_words = (E == 4 ? 2 : 1) * n;
     static constexpr uint32_t words = plane_words + (kShared + kWaves * kPriv) * SW;
@@ -1803,25 +1792,20 @@ __device__ __forceinline__ void col_eval_poly(const MonoCore &A, uint32_t ebits,
 template <int L, int LR, int SPLIT, int E>
 __device__ __forceinline__ uint4 priv_piece(const uint32_t *img, uint32_t wave, uint32_t q) {
     using G = Stage<L, LR, SPLIT, E>;
-    const uint32_t t = q / G::LPC, piece = q - t * G::LPC;
-    const uint32_t y = (G::W >> G::B0) - t;                   // in [1, W >> B0]
-    const int b = G::IW - int(32 - __builtin_clz(y - 1));    // IW - ceil(log2 y)
-    const uint32_t local = t - ((G::W >> G::B0) - (G::W >> b));
-    const uint32_t slot = G::n - (G::n >> b) + wave * (G::W >> (b + 1)) + local;
-    return reinterpret_cast<const uint4 *>(img)[slot * G::LPC + piece];
+    return reinterpret_cast<const uint4 *>(img)[G::SM::priv_index(wave, q, G::LPC)];
 }
 // 16-byte piece q of the layer-0 tables of wave `wave`'s phase-1 / -3 rows
 // (image slots wave * W/2 .. : contiguous, one coalesced read per wave)
 template <int L, int LR, int SPLIT, int E>
 __device__ __forceinline__ uint4 l0_piece(const uint32_t *img, uint32_t wave, uint32_t q) {
     using G = Stage<L, LR, SPLIT, E>;
-    return reinterpret_cast<const uint4 *>(img)[wave * G::kL0 * G::LPC + q];
+    return reinterpret_cast<const uint4 *>(img)[G::SM::l0_index(wave, q, G::LPC)];
 }
 template <int L, int LR, int SPLIT, int E>
 __device__ __forceinline__ const uint4 *shared_piece_ptr(const uint32_t *img_i, const uint32_t *img_f, uint32_t q) {
     using G = Stage<L, LR, SPLIT, E>;
     const uint32_t t = q / G::LPC, piece = q - t * G::LPC;
-    const uint32_t slot = t < G::kShI ? G::n - (G::n >> G::IW) + t : G::n - (G::n >> G::FLO) + (t - G::kShI);
+    const uint32_t slot = t < G::kShI ? G::n - (G::n >> G::IW) + t : G::n - (G::n >> G::FLO) + (t - G::kShI);  // SM::shared_table
     return reinterpret_cast<const uint4 *>(t < G::kShI ? img_i : img_f) + slot * G::LPC + piece;
 }
 // 16-byte piece q of the D tables (Stage::kD): layer b = q / PC of image t_i ^ t_f, group 0
@@ -1844,9 +1828,117 @@ __device__ __forceinline__ uint32_t clamp_piece(uint32_t q, uint32_t count) { re
 // layer of table slot t of a wave-private region (phases 1 and 3)
 template <int L, int LR, int SPLIT, int E>
 __device__ __forceinline__ uint32_t priv_layer(uint32_t t) {
-    using G = Stage<L, LR, SPLIT, E>;
-    const uint32_t y = (G::W >> G::B0) - t;
-    return uint32_t(G::IW - int(32 - __builtin_clz(y - 1)));
+    return Stage<L, LR, SPLIT, E>::SM::priv_layer(t);
+}
+
+// RS_MONO_LDS_DMA (the staged single-chunk encodes' preloaded entry): the tables go
+// from the images straight into LDS (global_load_lds_dwordx4), with no VGPR hop and no
+// ds_write_b128 pass.  A DMA instruction writes 1 KiB at a wave-uniform LDS address +
+// 16 bytes per lane, so the fill is linear: lane l of instruction kc fills 16-byte
+// position 64 kc + l of the region, and fetches the image piece that the slot maps put
+// there (rs_stage_map.hpp inv1 / inv0 / invS).  Slots, swizzle and every table read stay
+// as they are.  The DMAs are inline assembly: behind the builtin the compiler waits
+// vmcnt(0) before the next ds_read of the array, which would drain phase 3's DMAs at
+// phase 2's first table read.  The compiler does not count them, so (a) its own vmcnt
+// for the row loads waits for more than it needs, never less (the counter retires in
+// order), and (b) the tables' readiness is stated here, by dma_wait<N> with N derived
+// at each use.  Ordering: a wave reads its private region behind its
+// own covering vmcnt; the shared region behind every wave's vmcnt and remap 1's
+// barrier; a DMA over a region goes out only after the wave's reads of the old
+// contents have returned (lgkmcnt(0)).  Measured (profiles/r09a, 4 alternating rounds):
+// the headline encode 7.29-7.35 -> 7.13-7.17 us per launch in the probe, 7.57-7.72 ->
+// 7.35-7.48 us per step in the plain bench; LDS instructions -16 %, LDS bank conflicts
+// -94 %, VALU +4.5 % (the inverse maps), VGPRs 99 -> 68.  0 keeps the register-staged fill.
+#ifndef RS_MONO_LDS_DMA
+#define RS_MONO_LDS_DMA 1
+#endif
+// the LDS byte address of a pointer into the workgroup's LDS
+__device__ __forceinline__ uint32_t lds_addr(const uint32_t *p) {
+    return uint32_t(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) uint32_t *)p));
+}
+// One DMA instruction: every active lane fetches the 16 bytes at its `src` into LDS at
+// lds_dst + 16 * lane (lds_dst wave-uniform).  M0 holds the LDS address; the compiler
+// reserves M0 and does not keep it around a statement, so it is saved, set and
+// restored inside this one
+__device__ __forceinline__ void glds16(const uint4 *src, uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src), "s"(lds_dst)
+                 : "memory");
+}
+// the same with the source as a wave-uniform base (an SGPR pair) + each lane's 32-bit
+// byte offset: no 64-bit address arithmetic per lane
+__device__ __forceinline__ void glds16(const uint32_t *base, uint32_t byte_off, uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(byte_off), "s"(lds_dst), "s"(base)
+                 : "memory");
+}
+// wait until at most N of the wave's vector-memory operations (DMAs included) are pending
+template <int N>
+__device__ __forceinline__ void dma_wait() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// DMA fill of the first TABLES slots of a wave region at LDS address lds_dst.  KIND 1:
+// tables of layers B0.. of phase 1 or 3 (inv1); KIND 0: the layer-0 turn (inv0).  An
+// instruction whose positions lie in one layer (kc is a compile-time constant) has a
+// constant layer mask and image base.  Lanes past the region's end sit out: an active
+// DMA lane always writes, and what follows the region is the next wave's.
+// The source index of a position depends on the wave, the lane and kc, not on the image:
+// phase 3 fetches the pieces of the FFT image that phase 1 fetched of the IFFT image.
+// KEEP 1 leaves the indices in keep[] (pinned in VGPRs), KEEP 2 takes them from there
+// instead of computing them again.
+template <typename SM, uint32_t TABLES, int KIND, int KEEP = 0, size_t NK = 1>
+__device__ __forceinline__ void dma_priv(const uint32_t *img, uint32_t wave, uint32_t lane, uint32_t lds_dst,
+                                         uint32_t (&keep)[NK]) {
+    constexpr uint32_t N = TABLES * SM::SPC;
+    static_assert(TABLES <= SM::kPriv, "inside the wave's region");
+    static_assert(KEEP == 0 || NK == SM::insts(TABLES), "one kept index per instruction");
+    static_for<0, int(SM::insts(TABLES))>([&](auto kc_) {
+        constexpr uint32_t kc = decltype(kc_)::value;
+        const uint32_t p = lane + 64u * kc;
+        uint32_t idx;
+        if constexpr (KEEP == 2) {
+            idx = keep[kc];
+        } else if constexpr (KIND == 0) {
+            const auto s = SM::inv0(p);
+            idx = SM::l0_index(wave, s.t * SM::PC + s.piece);
+        } else {
+            constexpr uint32_t s_lo = 64u * kc / SM::SPC, s_hi = (64u * kc + 63u < N ? 64u * kc + 63u : N - 1u) / SM::SPC;
+            constexpr uint32_t k = SM::kSeq;
+            constexpr uint32_t m_lo = SM::layer_mask(s_lo, k), m_hi = SM::layer_mask(s_hi, k);
+            const uint32_t mask = m_lo == m_hi ? m_lo : SM::layer_mask(p / SM::SPC, k);
+            const auto s = SM::inv1_mask(p, mask);
+            idx = SM::priv_table_mask(wave, s.t, mask) * SM::PC + s.piece;
+        }
+        if constexpr (KEEP != 2) idx *= 16u;  // the lane's byte offset into the image (at most 2^11 tables of 80 bytes)
+        if constexpr (KEEP == 1) {
+            asm volatile("" : "+v"(idx));  // computed once, kept in a VGPR
+            keep[kc] = idx;
+        }
+        if (64u * kc + 63u < N || p < N) glds16(img, idx, lds_dst + 1024u * kc);
+    });
+}
+// DMA fill of the shared region by all WAVES waves: wave w's instruction kc fills
+// positions 64 (w + WAVES kc) .. of it
+template <typename SM, uint32_t WAVES>
+__device__ __forceinline__ void dma_shared(const uint32_t *img_i, const uint32_t *img_f, uint32_t wave, uint32_t lane,
+                                           uint32_t lds_dst) {
+    constexpr uint32_t N = SM::kShared * SM::SPC;
+    static_for<0, int((N + 64u * WAVES - 1u) / (64u * WAVES))>([&](auto kc_) {
+        constexpr uint32_t kc = decltype(kc_)::value;
+        const uint32_t blk = wave + WAVES * kc;
+        const uint32_t p = lane + 64u * blk;
+        if (p < N) {
+            const auto s = SM::invS(p);
+            glds16(reinterpret_cast<const uint4 *>(s.t < SM::kShI ? img_i : img_f) + SM::shared_table(s.t) * SM::PC +
+                       s.piece,
+                   lds_dst + 1024u * blk);
+        }
+    });
 }
 
 #ifndef RS_MONO_LDS_PF
@@ -2100,6 +2192,13 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
             constexpr int KP0 = G::B0 ? (LPC * G::kL0 + 63) / 64 : 1;
             constexpr int KP3 = G::kP3 ? (LPC * G::kP3 + 63) / 64 : 1;  // (guarded by q < LPC * kP3)
             constexpr int KSH = kSh ? (LPC * kSh + T - 1) / T : 1;  // (guarded by q < LPC * kSh)
+            // tables by LDS-DMA (RS_MONO_LDS_DMA above): the preloaded encode entry
+            constexpr bool kDma = RS_MONO_LDS_DMA && PRE && !G::kBasis && !kDerive3;
+            using SM = typename G::SM;
+            [[maybe_unused]] const uint32_t lds_priv = lds_addr(priv), lds_shared = lds_addr(shared);
+            // phase 3 covers phase 1's positions: its source indices are phase 1's, kept (dma_priv)
+            constexpr bool kKeep3 = kDma && !G::B0 && G::kP3 == G::kUp;
+            [[maybe_unused]] uint32_t didx[kKeep3 ? SM::insts(G::kUp) : 1];
             RS_MSTAMP(0);
             uint32_t ebits = 0, rbits = 0, lwv = 0;
             if constexpr (MASKS) {
@@ -2215,24 +2314,40 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
             // the region's end re-read its last piece and do not write it, so the
             // loads are unconditional); B0: layer 0's go into the region first, the
             // layers above when layer 0 has read them (run_seq's hook)
+            // kDma: the region's first contents (layer 0's turn with B0, else phase 1's
+            // tables) go by DMA; with B0 the layers above still pass through v1: they
+            // can enter the region only after layer 0 has read it (run_seq's hook), and a
+            // DMA issued there would have its whole fetch latency in front of layer 1
             uint4 v0[KP0], v1[KP1], vs[KSH];
-            auto issue_priv = [&]() {
+            auto issue_v1 = [&]() {
 #ifndef RS_MONO_SKIP_STAGE  // tools/mono_probe.hip ablation
-                if constexpr (G::B0)
-                    static_for<0, KP0>([&](auto kc) {
-                        const uint32_t q = clamp_piece(lane + 64u * decltype(kc)::value, LPC * G::kL0);
-                        v0[kc] = l0_piece<L, LR, PK, E>(img_i, wave, live ? q : q % LPC);
-                    });
                 static_for<0, KP1>([&](auto kc) {
                     const uint32_t q = clamp_piece(lane + 64u * decltype(kc)::value, LPC * G::kUp);
                     v1[kc] = priv_piece<L, LR, PK, E>(img_i, wave, live ? q : q % LPC);
                 });
 #endif
             };
+            auto issue_priv = [&]() {
+#ifndef RS_MONO_SKIP_STAGE
+                if constexpr (kDma) {
+                    if constexpr (G::B0) dma_priv<SM, G::kL0, 0>(img_i, wave, lane, lds_priv, didx);
+                    else dma_priv<SM, G::kUp, 1, kKeep3 ? 1 : 0>(img_i, wave, lane, lds_priv, didx);
+                    return;  // (B0: issue_v1 follows the shared region's DMA, see the wait below)
+                }
+                if constexpr (G::B0)
+                    static_for<0, KP0>([&](auto kc) {
+                        const uint32_t q = clamp_piece(lane + 64u * decltype(kc)::value, LPC * G::kL0);
+                        v0[kc] = l0_piece<L, LR, PK, E>(img_i, wave, live ? q : q % LPC);
+                    });
+#endif
+                issue_v1();
+            };
             // the shared region: every thread of the workgroup loads and writes pieces
             auto issue_shared = [&]() {
 #ifndef RS_MONO_SKIP_STAGE
-                if constexpr (kSh > 0)
+                if constexpr (kDma) {
+                    if constexpr (kSh > 0) dma_shared<SM, G::kWaves>(img_i, img_f, wave, lane, lds_shared);
+                } else if constexpr (kSh > 0)
                     static_for<0, KSH>([&](auto kc) {
                         const uint32_t q = clamp_piece(threadIdx.x + T * decltype(kc)::value, LPC * kSh);
                         if constexpr (kSh == G::kShared) {
@@ -2284,6 +2399,7 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
                 else issue_rows(kIO{});
                 issue_priv();
                 issue_shared();
+                if constexpr (kDma && G::B0) issue_v1();  // behind every DMA of the prologue
                 issue_quad_tabs();
                 if constexpr (VERIFY) verify_issue<L, LR, PK, E>(A, io, sb, vp, lane, wave);
                 if constexpr (PRE) {
@@ -2344,7 +2460,9 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
 #endif
             };
 #ifndef RS_MONO_SKIP_STAGE
-            if (!skip) {  // (a skipping wave's region is written by phase 3's tables before use)
+            if constexpr (kDma) {
+                // nothing to write: the DMAs fill the regions (waited for below, behind the rows)
+            } else if (!skip) {  // (a skipping wave's region is written by phase 3's tables before use)
                 if constexpr (G::B0 && !HALF_F)
                     static_for<0, KP0>([&](auto kc) {
                         const uint32_t q = lane + 64u * decltype(kc)::value;
@@ -2365,10 +2483,11 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
                     for (int k = 0; k < 8; ++k) __builtin_amdgcn_s_sleep(127);
             }
 #endif
-            static_for<0, KSH>([&](auto kc) {
-                const uint32_t q = threadIdx.x + T * decltype(kc)::value;
-                if (q < LPC * kSh) G::put(shared, q, vs[kc], [](uint32_t p) { return G::atS(p); });
-            });
+            if constexpr (!kDma)
+                static_for<0, KSH>([&](auto kc) {
+                    const uint32_t q = threadIdx.x + T * decltype(kc)::value;
+                    if (q < LPC * kSh) G::put(shared, q, vs[kc], [](uint32_t p) { return G::atS(p); });
+                });
             write_quad_tabs();  // (wave-private: read back by this wave only)
 #endif
             C cb;  // kMonoHalfF: the upper half's rows
@@ -2381,12 +2500,30 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
             } else {
                 finish_col<L, LR, DEC || HSC>(w, okm, &st, c, lane, io);
             }
+            // kDma, wait 1: before phase 1's first table read (the wave's own region) and
+            // before remap 1's barrier, which hands the shared region to phase 2, every
+            // DMA of the prologue must have landed.  Issue order: rows, the region's
+            // DMAs, the shared region's DMA, then with B0 the KP1 loads of v1 -- plain
+            // loads that every wave issues unconditionally and that may stay in flight
+            // until the hook writes them: N = KP1.  Without B0 the DMAs are the wave's
+            // newest vector-memory operations: N = 0.  (A wave with no lane in the
+            // shared region has fewer operations pending, never more: the count holds.)
+            if constexpr (kDma) dma_wait<G::B0 ? KP1 : 0>();
             RS_MSTAMP(1);
             // phase-3 tables: requested when phase 1 ends, written over this wave's
             // phase-1 tables when phase 2 ends
             uint4 v3[KP3];
             auto issue3 = [&]() {
                 if (reuse3) return;
+                if constexpr (kDma) {
+                    // over the wave's phase-1 tables (WAR): every layer of phase 1 has used
+                    // its tables, and this wait states that the reads have returned
+                    if constexpr (G::kP3 > 0) {
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        dma_priv<SM, G::kP3, 1, kKeep3 ? 2 : 0>(img_f, wave, lane, lds_priv, didx);
+                    }
+                    return;
+                }
                 if constexpr (G::kP3 > 0)
                 static_for<0, KP3>([&](auto kc) {
                     const uint32_t q = lane + 64u * decltype(kc)::value;
@@ -2413,6 +2550,16 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
                             if (q < PC * G::kP3) reinterpret_cast<uint4 *>(priv)[G::at1(q)] = x[kc];
                         });
                     }
+                    return;
+                }
+                if constexpr (kDma) {
+                    // wait 2: before remap 2 and phase 3's first table read, issue3's DMAs
+                    // must have landed; they stayed in flight across remap 1 and the top
+                    // phases.  Since them the wave has issued, with B0, the KP0 loads of v4
+                    // (issue4: plain loads, unconditional, in flight until the layer-0
+                    // turn): N = KP0; without B0 nothing: N = 0.  Every wave of an encode
+                    // comes through here, so no DMA is pending when a wave ends
+                    dma_wait<G::B0 ? KP0 : 0>();
                     return;
                 }
                 static_for<0, KP3>([&](auto kc) {
