@@ -36,6 +36,10 @@
  *   pattern per stripe): the decode that also rebuilds missing recovery shards
  *   rs_update_device (+ _batch): a partial-stripe write applied to the recovery
  *   shards in place, from the changed originals' deltas alone
+ *   rs_verify_device (+ _batch): which recovery shards no longer agree with the
+ *   originals
+ *   rs_locate_device (+ _batch): the verify that also names the one corrupt
+ *   original of a stripe whose recovery shards all disagree
  *
  * Thread-safety: a context may be shared by threads (like DefaultEngine:
  * Send + Sync, src/lib.rs:385-409): calls on one context are serialized on the
@@ -536,6 +540,119 @@ rs_status rs_verify_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  uint64_t recovery_stride, uint64_t recovery_stripe_stride,
                                  const uint8_t *recovery_check, uint8_t *d_mismatch, void *stream, rs_error *err);
 rs_status rs_verify_set_fused(rs_context *ctx, int mode);
+
+/* ---- locate: which original of a stripe is corrupt? ----
+ * rs_verify_device flags the recovery rows that disagree with the originals.
+ * When an ORIGINAL has rotted every recovery row is flagged and nothing says
+ * which shard to hand to rs_repair_device* as absent.  This call does: it is the
+ * verify plus one word per stripe.
+ *   The algebra.  Let D_j = recovery_j ^ encode(originals)_j.  If original i alone
+ * is wrong by e (one element per column), D_j = G[j][i] * e in every column and
+ * for every row j, with G the coefficient matrix of rs_update_device.  In a
+ * column where e != 0 the ratio D_j1 / D_j0 of two rows equals G[j1][i] /
+ * G[j0][i], and that ratio names i: the code is MDS, so no 2 x 2 minor of G
+ * vanishes.
+ *   Arguments, strides (0 = dense), alignment rules, the byte-wise path, the
+ * block and tail layout, the HOST mask recovery_check (NULL = every row; rows
+ * marked 0 are never read; ONE mask for every stripe of a batch) and d_mismatch
+ * are those of rs_verify_device[_batch].  d_located: DEVICE array of one int32_t
+ * per stripe (4-byte aligned).  Asynchronous on `stream`, scratch per (context,
+ * stream).
+ *   Result: after the call every byte of d_mismatch and every word of d_located
+ * is defined.  d_mismatch is exactly what rs_verify_device_batch writes for the
+ * same arguments.  d_located[b] is
+ *   RS_LOCATE_CLEAN    no selected row of stripe b differs.
+ *   RS_LOCATE_ROWS     at least one selected row differs and at least one agrees.
+ *                      A single corrupt original would make every selected row
+ *                      differ, so that is ruled out; the flags name the differing
+ *                      rows, as after a verify.  NOT proven: that the originals
+ *                      are intact.  Two or more corrupt originals can leave some
+ *                      recovery row matching by coincidence (their contributions
+ *                      cancel in that row).  The coefficients of low positions lie
+ *                      in small subfields, so this happens more often than 2^-16
+ *                      per row and column: seen at 128:128 and 128:1024 with
+ *                      original 0 off by 1 and the last original off by 2 in one
+ *                      column.  A row that agrees vouches for no original.
+ *   i in [0, original_count)
+ *                      every selected row differs, and in every column and for
+ *                      every selected row j, D_j = G[j][i] * e for one e per
+ *                      column.  With two or more rows selected (the call takes no
+ *                      fewer) that i is unique.  Handing original i to
+ *                      rs_repair_device* as absent heals the stripe.
+ *   RS_LOCATE_UNKNOWN  every selected row differs and no such i exists: two or
+ *                      more corrupt originals, an original plus recovery rows,
+ *                      every recovery row corrupt, ...
+ * The value depends on the stripe's bytes and the mask alone, not on how it is
+ * computed.  Nothing is written but d_located (`stripes` words) and the flags.
+ *   How far to trust an i.  With c selected rows, up to c - 1 corrupt shards
+ * (originals and selected recovery rows alike) are never attributed to a wrong
+ * single original: that would need a vanishing c x c minor of [G | I], and an
+ * MDS code has none.  With exactly two selected
+ * rows, two corrupt originals CAN be attributed to a third.  Select three rows or
+ * more where the stripe has them.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * d_recovery, d_located or d_mismatch -> RS_ERR_INVALID_ARGUMENT; rs_validate; the
+ * two row strides; recovery_count < 2 or a mask that selects fewer than two rows
+ * -> RS_ERR_INVALID_ARGUMENT (rs_verify_device is the call for those); a shape
+ * beyond the coefficient table's bound, original_count >
+ * RS_LOCATE_MAX_ORIGINALS or original_count x recovery_count >
+ * RS_LOCATE_MAX_COEFFICIENTS -> RS_ERR_INVALID_ARGUMENT.  stripes == 0: RS_OK,
+ * nothing launched or written, the context not touched.
+ *   The table.  log G[j][i] for every i, recovery_count x original_count uint16_t
+ * (32 MiB at the bound), is built by the first locate of a (rate,
+ * original_count, recovery_count) on a stream: the update's coefficient step over
+ * slabs of 256 consecutive originals (the unit stripe of the slab, 512 bytes per
+ * shard, the library's encode of it, the logs), so its scratch stays at the
+ * update's size.  It is kept with the stream's scratch until another shape
+ * arrives or rs_release_stream_scratch frees it, and depends on neither the data
+ * nor the mask.  The update's own table is a different one and is not disturbed.
+ *   Launches, always the unfused verify's: the flags zeroed, the encode of the
+ * selected span into per-stream scratch (the whole batch where the batch encode is
+ * one launch, else stripe by stripe), k_verify_rows; then k_locate_find, one
+ * workgroup per stripe (CLEAN / ROWS from the flags, else the first column where
+ * the first selected row differs, the log ratio against the second selected row
+ * there, and the search of the two table rows for it), and k_locate_confirm over
+ * every selected row and pack (D_j == (D_j0 / G[j0][i]) * G[j][i], the products the
+ * engine's own), whose workgroups leave at once for a stripe without a candidate.
+ *   Measured (tools/locate_time.py, profiles/locate/locate_time.txt; 1024:1024,
+ * every row, us per call; clean = no stripe differs, corrupt = one corrupt
+ * original in every stripe, cold = the table rebuilt; encode =
+ * rs_encode_device[_batch] of the same shape, whose kernels are the parent
+ * commit's instruction for instruction -- the leg run on the parent's build read
+ * 8.28 / 201.8 / 102.6; spread = max - min of the encode leg's five rounds; in
+ * brackets the ratio to the encode):
+ *     shape                clean         corrupt       cold          unfused verify  encode  spread
+ *     1 KiB, one stripe    15.78 (2.14)  23.00 (3.12)  73.60 (9.98)  13.55 (1.84)      7.37    0.42
+ *     1 KiB, 64 stripes    239.8 (1.19)  265.5 (1.32)  300.5 (1.49)  233.7 (1.16)     201.6    2.33
+ *     64 KiB, one stripe   125.9 (1.29)  163.5 (1.68)  190.7 (1.95)  120.6 (1.24)      97.6    0.34
+ * A clean call costs the unfused verify plus TWO small launches (+2.2 / +6.1 /
+ * +5.3 us), one more than hoped for: the call is asynchronous, so the confirm is
+ * launched whether or not a stripe has a candidate.  A corrupt original in every
+ * stripe adds 7.2 / 25.7 / 37.6 us: the confirm is one more read of the scratch
+ * and the caller's rows, as expected (27 us against k_verify_rows' 31 over 64
+ * stripes); the find's candidate path, one workgroup per stripe, adds 4 us at
+ * 1 KiB and 14 us at 64 KiB.  The fused verify (10.55 / 240.5 us) stays the
+ * cheaper first pass of a scrub that expects no corrupt originals.  DESIGN.md
+ * "Locate" has the rest.
+ *   Not covered: one corrupt original together with corrupt recovery rows
+ * (majority logic over row subsets); a mask per stripe; stripes with missing
+ * originals; writing the correction e back; the host pipeline, the object API and
+ * the sharded classes; a fused form on k_mono_verify. */
+#define RS_LOCATE_CLEAN (-1)
+#define RS_LOCATE_ROWS (-2)
+#define RS_LOCATE_UNKNOWN (-3)
+#define RS_LOCATE_MAX_ORIGINALS 4096u
+#define RS_LOCATE_MAX_COEFFICIENTS (1u << 24)
+rs_status rs_locate_device(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                           uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
+                           const void *d_recovery, uint64_t recovery_stride, const uint8_t *recovery_check,
+                           int32_t *d_located, uint8_t *d_mismatch, void *stream, rs_error *err);
+rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                 uint64_t shard_bytes, uint64_t stripes, const void *d_original,
+                                 uint64_t original_stride, uint64_t original_stripe_stride, const void *d_recovery,
+                                 uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                 const uint8_t *recovery_check, int32_t *d_located, uint8_t *d_mismatch, void *stream,
+                                 rs_error *err);
 
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x

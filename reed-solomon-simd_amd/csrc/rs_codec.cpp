@@ -179,6 +179,17 @@ struct VerifyWs {
     bool mask_valid = false;
 };
 
+// What rs_locate_device* keeps per stream (DESIGN.md "Locate"): the table of
+// log G[j][i] over every original i with the shape it was built for, and the
+// scratch of its coefficient step.  (The encode's scratch matrix and the mask are
+// the verify's, VerifyWs.)
+struct LocateWs {
+    DevBuf unit, coef, logs;
+    bool valid = false;  // `logs` holds the table of (high, n, m)
+    int high = 0;
+    uint64_t n = 0, m = 0;
+};
+
 // Device scratch of one stream's calls.  Calls on one stream execute in order,
 // so one workspace per (context, stream) makes concurrent calls on different
 // streams safe (rs_mi355x.h "Threading and streams").
@@ -188,9 +199,11 @@ struct Workspace {
     PinnedBuf h_state_pinned;  // source of the erasure-state copy of large decodes
     std::unique_ptr<UpdateWs> upd;  // rs_update_device*, made by the stream's first update
     std::unique_ptr<VerifyWs> ver;  // rs_verify_device*, made by the stream's first masked or unfused verify
+    std::unique_ptr<LocateWs> loc;  // rs_locate_device*, made by the stream's first locate
     void swap(Workspace &o) {
         upd.swap(o.upd);
         ver.swap(o.ver);
+        loc.swap(o.loc);
         for (int k = 0; k < 4; ++k) buf[k].swap(o.buf[k]);
         rowinfo.swap(o.rowinfo);
         state.swap(o.state);
@@ -1887,6 +1900,32 @@ struct VerifyCall {
     uint8_t *d_flags;                    // stripes x M
 };
 
+// The mask of a verify or locate on the device, kept with the stream's scratch
+// (VerifyWs) and copied on `s` only when it changes: *d_sel = M selection bytes,
+// *d_list = the nsel selected rows in order.
+void verify_mask(Workspace &ws, const uint8_t *host_mask, uint32_t M, uint32_t nsel, hipStream_t s,
+                 const uint8_t **d_sel, const uint32_t **d_list) {
+    if (!ws.ver) ws.ver.reset(new VerifyWs);
+    VerifyWs &v = *ws.ver;
+    std::vector<uint8_t> mask(M);
+    for (uint32_t j = 0; j < M; ++j) mask[j] = host_mask[j] != 0;
+    const size_t list_off = round_up(M, 4), bytes = list_off + size_t(nsel) * 4;
+    if (!v.mask_valid || v.mask != mask) {
+        v.mask_valid = false;
+        uint8_t *h = v.h_mask.get(bytes);
+        std::memcpy(h, mask.data(), M);
+        uint32_t *list = reinterpret_cast<uint32_t *>(h + list_off);
+        for (uint32_t j = 0, k = 0; j < M; ++j)
+            if (mask[j]) list[k++] = j;
+        check(hipMemcpyAsync(v.d_mask.get(bytes), h, bytes, hipMemcpyHostToDevice, s));
+        v.h_mask.copied_on(s);
+        v.mask.swap(mask);
+        v.mask_valid = true;
+    }
+    *d_sel = static_cast<const uint8_t *>(v.d_mask.p);
+    *d_list = reinterpret_cast<const uint32_t *>(*d_sel + list_off);
+}
+
 // The caller has checked that the mask selects a row and that stripes > 0.
 void verify_dev(rs_context *ctx, Workspace &ws, bool high, Geom g, const VerifyCall &V, hipStream_t s) {
     const uint32_t M = uint32_t(V.M);
@@ -1900,27 +1939,7 @@ void verify_dev(rs_context *ctx, Workspace &ws, bool high, Geom g, const VerifyC
     check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
     const uint8_t *d_sel = nullptr;    // M selection bytes (the fused kernel)
     const uint32_t *d_list = nullptr;  // the nsel selected rows (k_verify_rows)
-    if (nsel < M) {
-        if (!ws.ver) ws.ver.reset(new VerifyWs);
-        VerifyWs &v = *ws.ver;
-        std::vector<uint8_t> mask(M);
-        for (uint32_t j = 0; j < M; ++j) mask[j] = V.mask[j] != 0;
-        const size_t list_off = round_up(M, 4), bytes = list_off + size_t(nsel) * 4;
-        if (!v.mask_valid || v.mask != mask) {
-            v.mask_valid = false;
-            uint8_t *h = v.h_mask.get(bytes);
-            std::memcpy(h, mask.data(), M);
-            uint32_t *list = reinterpret_cast<uint32_t *>(h + list_off);
-            for (uint32_t j = 0, k = 0; j < M; ++j)
-                if (mask[j]) list[k++] = j;
-            check(hipMemcpyAsync(v.d_mask.get(bytes), h, bytes, hipMemcpyHostToDevice, s));
-            v.h_mask.copied_on(s);
-            v.mask.swap(mask);
-            v.mask_valid = true;
-        }
-        d_sel = static_cast<const uint8_t *>(v.d_mask.p);
-        d_list = reinterpret_cast<const uint32_t *>(d_sel + list_off);
-    }
+    if (nsel < M) verify_mask(ws, V.mask, M, nsel, s, &d_sel, &d_list);
     // the encode's transform: does it run as the staged single-chunk column kernel
     // (one launch for a batch, encode_high / encode_low)?
     const uint32_t n = uint32_t(next_pow2(high ? V.M : V.N)), L = ilog2(n);
@@ -1973,6 +1992,103 @@ void verify_dev(rs_context *ctx, Workspace &ws, bool high, Geom g, const VerifyC
         R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
         R.fmt = g.fmt;
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(R, s); });
+    }
+}
+
+// ---- locate (rs_locate_device*, DESIGN.md "Locate") -------------------------
+// Originals per slab of the coefficient step: the unit stripe's shards are 64 *
+// ceil(slab / 32) bytes, the update's scratch at its largest direct count.
+constexpr uint32_t kLocateSlab = kUpdateDirectCap;
+
+// log G[j][i] for every original i of (high, N, M), built on `s` unless the
+// stream's workspace holds it already.
+const uint16_t *locate_table(rs_context *ctx, Workspace &ws, bool high, uint64_t N, uint64_t M, hipStream_t s) {
+    if (!ws.loc) ws.loc.reset(new LocateWs);
+    LocateWs &l = *ws.loc;
+    if (l.valid && l.high == int(high) && l.n == N && l.m == M) return static_cast<const uint16_t *>(l.logs.p);
+    l.valid = false;
+    if (!ctx->d_log) {  // as the context's first update
+        const rs::GfTables &T = rs::tables();
+        check(hipMalloc(&ctx->d_log, T.log.size() * 2));
+        check(hipMemcpy(ctx->d_log, T.log.data(), T.log.size() * 2, hipMemcpyHostToDevice));
+    }
+    const uint64_t W = 64 * ((std::min<uint64_t>(kLocateSlab, N) + 31) / 32);
+    uint8_t *unit = static_cast<uint8_t *>(l.unit.get(N * W));
+    uint8_t *coef = static_cast<uint8_t *>(l.coef.get(M * W));
+    uint16_t *logs = static_cast<uint16_t *>(l.logs.get(round_up(M * N * 2, 4)));
+    const Geom g = device_geom(W, 0, 0, 0, {unit, coef});
+    for (uint64_t i0 = 0; i0 < N; i0 += kLocateSlab) {
+        const uint32_t k = uint32_t(std::min<uint64_t>(kLocateSlab, N - i0));
+        check(hipMemsetAsync(unit, 0, N * W, s));
+        update_launch(s, k, [&] { return rs::launch_locate_unit(unit, W, uint32_t(i0), k, s); });
+        if (high) encode_high(ctx, ws, g, N, M, unit, coef, s);
+        else encode_low(ctx, ws, g, N, M, unit, coef, s);
+        update_launch(s, M * k * 4, [&] {
+            return rs::launch_locate_log(coef, W, uint32_t(M), uint32_t(i0), k, uint32_t(N), ctx->d_log, logs, s);
+        });
+    }
+    l.high = int(high), l.n = N, l.m = M;
+    l.valid = true;
+    return logs;
+}
+
+struct LocateCall : VerifyCall {
+    int32_t *d_located;  // one per stripe
+};
+
+// The caller has checked that the mask selects two rows at least, the shape bound
+// and that stripes > 0.  The unfused verify (verify_dev) with two more launches per
+// group of stripes while the encode is still in scratch.
+void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V, hipStream_t s) {
+    const uint32_t M = uint32_t(V.M);
+    uint32_t lo = 0, hi = M, nsel = M;
+    if (V.mask) {
+        lo = M, hi = 0, nsel = 0;
+        for (uint32_t j = 0; j < M; ++j)
+            if (V.mask[j]) lo = std::min(lo, j), hi = j + 1, ++nsel;
+    }
+    const uint16_t *logs = locate_table(ctx, ws, high, V.N, V.M, s);
+    check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
+    const uint8_t *d_sel = nullptr;
+    const uint32_t *d_list = nullptr;
+    if (nsel < M) verify_mask(ws, V.mask, M, nsel, s, &d_sel, &d_list);
+    const uint32_t n = uint32_t(next_pow2(high ? V.M : V.N)), L = ilog2(n);
+    const uint32_t C = uint32_t(((high ? V.N : V.M) + n - 1) / n);
+    const bool column = use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+    const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+
+    if (!ws.ver) ws.ver.reset(new VerifyWs);
+    const uint64_t W = g.stride, group = column ? kMaxBatchStripes : 1;
+    uint8_t *enc = static_cast<uint8_t *>(ws.ver->enc.get(std::min<uint64_t>(group, V.stripes) * V.M * W));
+    Geom ge = g;
+    ge.rec_stride = W;
+    ge.orig_bstride = V.orig_bstride;
+    ge.rec_bstride = V.M * W;
+    for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
+        ge.stripes = uint32_t(std::min<uint64_t>(group, V.stripes - b0));
+        const uint8_t *o = V.d_orig + b0 * V.orig_bstride;
+        if (high) encode_high(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
+        else encode_low(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
+        rs::VerifyRowsArgs R;
+        R.want = enc, R.want_stride = W, R.want_bstride = V.M * W;
+        R.have = V.d_rec + b0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
+        R.rows = d_list, R.nrows = nsel, R.packs = g.packs, R.stripes = ge.stripes;
+        R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
+        R.fmt = g.fmt;
+        update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(R, s); });
+        rs::LocateArgs A;
+        A.want = R.want, A.want_stride = W, A.want_bstride = R.want_bstride;
+        A.have = R.have, A.have_stride = R.have_stride, A.have_bstride = R.have_bstride;
+        A.rows = d_list, A.nsel = nsel, A.packs = g.packs, A.stripes = ge.stripes;
+        A.N = uint32_t(V.N), A.M = M;
+        A.flags = R.flags, A.flag_bstride = V.M;
+        A.located = V.d_located + b0;
+        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
+        A.fmt = g.fmt;
+        // find: the flags and one word per stripe; a stripe with a candidate reads up to
+        // two rows and two table rows more.  confirm: as the compare, where it runs at all
+        update_launch(s, (V.M + 4) * uint64_t(ge.stripes), [&] { return rs::launch_locate_find(A, s); });
+        update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_locate_confirm(A, s); });
     }
 }
 
@@ -2974,6 +3090,53 @@ rs_status rs_verify_set_fused(rs_context *ctx, int mode) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->verify_fused = mode != 0;
     return RS_OK;
+}
+
+// ---- locate: the one corrupt original of a stripe (include/rs_mi355x.h) ----
+
+rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, uint64_t stripes,
+                                 const void *d_orig, uint64_t orig_stride, uint64_t orig_stripe_stride,
+                                 const void *d_rec, uint64_t rec_stride, uint64_t rec_stripe_stride,
+                                 const uint8_t *recovery_check, int32_t *d_located, uint8_t *d_mismatch, void *stream,
+                                 rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_located) || !ptr_ok(d_mismatch))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    uint64_t nsel = M;  // a ratio needs two rows; fewer: rs_verify_device
+    if (recovery_check) {
+        nsel = 0;
+        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
+    }
+    if (nsel < 2) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                      0, 0, recovery_check, d_mismatch},
+                     d_located};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        locate_dev(ctx, sw.w, high != 0, g, V, s);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_locate_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const void *d_orig,
+                           uint64_t orig_stride, const void *d_rec, uint64_t rec_stride,
+                           const uint8_t *recovery_check, int32_t *d_located, uint8_t *d_mismatch, void *stream,
+                           rs_error *err) {
+    return rs_locate_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
+                                  d_located, d_mismatch, stream, err);
 }
 
 // ---- encoder ----------------------------------------------------------------

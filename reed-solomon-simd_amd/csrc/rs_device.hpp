@@ -477,6 +477,43 @@ struct VerifyRowsArgs {
 };
 hipError_t launch_verify_rows(const VerifyRowsArgs &A, hipStream_t stream);
 
+// ---- locate (rs_locate_device*, rs_locate.hip; DESIGN.md "Locate") ----------
+// The coefficient step over a slab of consecutive originals i0 .. i0 + count - 1:
+// launch_locate_unit writes the slab's unit stripe into zeroed rows of `stride` =
+// 64 * ceil(count / 32) bytes (element c of row i0 + c = 1); launch_locate_log
+// turns its encode into logs[j * pitch + i0 + c] (pitch = original_count: the
+// slabs fill one M x N table), element 0 as kUpdateNoCoef.
+hipError_t launch_locate_unit(uint8_t *unit, uint64_t stride, uint32_t i0, uint32_t count, hipStream_t stream);
+hipError_t launch_locate_log(const uint8_t *coef, uint64_t stride, uint32_t rows, uint32_t i0, uint32_t count,
+                             uint32_t pitch, const uint16_t *log_table, uint16_t *logs, hipStream_t stream);
+// The values of located[] below zero (include/rs_mi355x.h RS_LOCATE_*).
+constexpr int32_t kLocateClean = -1, kLocateRows = -2, kLocateUnknown = -3;
+// After the unfused verify of `stripes` stripes (want: the encode in scratch, have:
+// the caller's recovery matrix, flags: what k_verify_rows stored over zeroes).
+// launch_locate_find (grid = stripes) writes every located[b]: kLocateClean /
+// kLocateRows from the flags, else the candidate original or kLocateUnknown.
+// launch_locate_confirm (grid = pack tiles, row groups, stripes <= 65535) checks
+// the candidates over every selected row and pack and stores kLocateUnknown where
+// one is refuted.  rows: the nsel >= 2 selected rows in order (nullptr: every row).
+struct LocateArgs {
+    const uint8_t *want = nullptr, *have = nullptr;
+    uint64_t want_stride = 0, have_stride = 0;
+    uint64_t want_bstride = 0, have_bstride = 0;  // stripe b: + b * bstride
+    const uint32_t *rows = nullptr;
+    uint32_t nsel = 0, packs = 0, stripes = 1;
+    uint32_t N = 0, M = 0;  // original_count, recovery_count
+    uint32_t rows_per_group = 1;
+    const uint8_t *flags = nullptr;
+    uint64_t flag_bstride = 0;
+    int32_t *located = nullptr;
+    const uint16_t *logs = nullptr;       // log G[j][i] at j * N + i, 4-byte aligned
+    const uint16_t *log_table = nullptr;  // log of every element (rs_context::d_log)
+    const uint32_t *lut = nullptr;        // perm tables by log factor (rs_context::d_lut)
+    ShardFormat fmt;
+};
+hipError_t launch_locate_find(const LocateArgs &A, hipStream_t stream);
+hipError_t launch_locate_confirm(const LocateArgs &A, hipStream_t stream);
+
 // x[rows] *= exp(log_m) over `blocks` 64-byte blocks.
 hipError_t launch_mul(uint8_t *rows, uint64_t blocks, const uint32_t *lut_entry, hipStream_t stream);
 

@@ -1,0 +1,217 @@
+// Kernels of a locate (rs_locate_device*, DESIGN.md "Locate"): which single
+// original of a stripe is corrupt?
+//
+// With D_j = recovery_j ^ encode(originals)_j and original i alone wrong by e (an
+// element per column), D_j = G[j][i] * e in every column and for every row j
+// (G: the update's coefficient matrix, rs_update.hip).  After the unfused verify
+// (the encode in scratch, k_verify_rows' flags):
+//
+//   k_coef_unit_slab / k_coef_log_slab   the update's coefficient step over a slab
+//                      of consecutive originals: the table log G[j][i], M x N
+//   k_locate_find      one workgroup per stripe: CLEAN / ROWS from the flags; else
+//                      the first column with D_j0 != 0, the log ratio of D_j1 and
+//                      D_j0 there (j0, j1: the first two selected rows), and the i
+//                      whose two table entries have that ratio
+//   k_locate_confirm   D_j == (D_j0 / G[j0][i]) * G[j][i] over every selected row and
+//                      pack of the stripes that name an i; a refutation stores
+//                      RS_LOCATE_UNKNOWN
+#include <cstdio>
+
+#include "rs_device.hpp"
+#include "rs_gf.hpp"
+
+namespace rs {
+namespace {
+
+// (rs_update.hip) a load through the constant address space from a wave-uniform
+// address goes through the scalar cache into SGPRs
+typedef const __attribute__((address_space(4))) uint32_t *ConstWords;
+__device__ __forceinline__ ConstWords const_words(const void *p) {
+    return (ConstWords)(reinterpret_cast<uintptr_t>(p));
+}
+
+constexpr int kTableWords = 20;  // words of one perm table (gf_tables.hpp kPermWords)
+constexpr uint32_t kNoLog = kUpdateNoCoef;
+constexpr uint32_t kFindThreads = 256;
+constexpr uint32_t kFindUnroll = 4;
+
+// Element c of the slab (original i0 + c) = 1, in the unit stripe's layout
+// (rs_device.hpp launch_update_unit).
+__global__ void k_coef_unit_slab(uint8_t *unit, uint64_t stride, uint32_t i0, uint32_t count) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= count) return;
+    unit[uint64_t(i0 + c) * stride + (c >> 5) * 64u + (c & 31u)] = 1;
+}
+
+// logs[j * pitch + i0 + c] = log of element c of recovery row j; log[0] = kNoLog.
+__global__ void k_coef_log_slab(const uint8_t *coef, uint64_t stride, uint32_t rows, uint32_t i0, uint32_t count,
+                                uint32_t pitch, const uint16_t *log_table, uint16_t *logs) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+    if (c >= count || j >= rows) return;
+    const uint8_t *p = coef + uint64_t(j) * stride + (c >> 5) * 64u + (c & 31u);
+    logs[uint64_t(j) * pitch + i0 + c] = log_table[uint32_t(p[0]) | uint32_t(p[32]) << 8];
+}
+
+// D of pack io of row j of stripe-relative bases want / have.
+__device__ __forceinline__ void ld_syndrome(const LocateArgs &A, const uint8_t *want, const uint8_t *have, uint32_t j,
+                                            const PackIO &io, uint32_t &dl, uint32_t &dh) {
+    const uint8_t *w = want + uint64_t(j) * A.want_stride + io.lo;
+    const uint8_t *h = have + uint64_t(j) * A.have_stride + io.lo;
+    dl = ld_word(w, io) ^ ld_word(h, io);
+    dh = ld_word(w + io.hi_delta, io) ^ ld_word(h + io.hi_delta, io);
+}
+
+// One workgroup per stripe; every branch below is uniform over the workgroup.
+__global__ __launch_bounds__(kFindThreads) void k_locate_find(const LocateArgs A) {
+    __shared__ uint32_t s_count, s_pack, s_found;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t b = blockIdx.x;
+    if (tid == 0) s_count = 0, s_pack = 0xFFFFFFFFu, s_found = 0xFFFFFFFFu;
+    __syncthreads();
+    // unselected rows' flags are zero: the sum counts the selected rows that differ
+    const uint8_t *flags = A.flags + b * A.flag_bstride;
+    uint32_t c = 0;
+    for (uint32_t j = tid; j < A.M; j += kFindThreads) c += flags[j] != 0;
+    if (c) atomicAdd(&s_count, c);
+    __syncthreads();
+    const uint32_t differ = s_count;
+    if (differ < A.nsel) {  // most stripes of a scrub end here
+        if (tid == 0) A.located[b] = differ ? kLocateRows : kLocateClean;
+        return;
+    }
+    const uint32_t j0 = A.rows ? A.rows[0] : 0u, j1 = A.rows ? A.rows[1] : 1u;
+    const uint8_t *want = A.want + b * A.want_bstride, *have = A.have + b * A.have_bstride;
+    // the first pack in which row j0 differs: kFindUnroll packs per thread between two barriers
+    for (uint32_t base = 0; base < A.packs; base += kFindThreads * kFindUnroll) {
+        uint32_t first = 0xFFFFFFFFu;
+#pragma unroll
+        for (uint32_t k = kFindUnroll; k-- > 0;) {
+            const uint32_t pk = base + k * kFindThreads + tid;
+            uint32_t dl = 0, dh = 0;
+            if (pk < A.packs) ld_syndrome(A, want, have, j0, pack_io(A.fmt, pk), dl, dh);
+            if (dl | dh) first = pk;
+        }
+        if (__syncthreads_or(first != 0xFFFFFFFFu)) {
+            if (first != 0xFFFFFFFFu) atomicMin(&s_pack, first);
+            break;
+        }
+    }
+    __syncthreads();
+    const uint32_t pk = s_pack;
+    int32_t result = kLocateUnknown;
+    if (pk < A.packs) {
+        const PackIO io = pack_io(A.fmt, pk);
+        uint32_t l0, h0, l1, h1;
+        ld_syndrome(A, want, have, j0, io, l0, h0);
+        ld_syndrome(A, want, have, j1, io, l1, h1);
+        uint32_t k = 0;  // the pack's first element with D_j0 != 0
+        while (k < 3 && !(((l0 | h0) >> (8 * k)) & 0xFFu)) ++k;
+        const uint32_t d0 = ((l0 >> (8 * k)) & 0xFFu) | ((h0 >> (8 * k)) & 0xFFu) << 8;
+        const uint32_t d1 = ((l1 >> (8 * k)) & 0xFFu) | ((h1 >> (8 * k)) & 0xFFu) << 8;
+        if (d0 && d1) {  // D_j1 = 0 where D_j0 != 0: no single original (no coefficient is the sentinel's)
+            const uint32_t ratio = (uint32_t(A.log_table[d1]) + 65535u - A.log_table[d0]) % 65535u;
+            const uint16_t *r0 = A.logs + uint64_t(j0) * A.N, *r1 = A.logs + uint64_t(j1) * A.N;
+            for (uint32_t i = tid; i < A.N; i += kFindThreads) {
+                const uint32_t g0 = r0[i], g1 = r1[i];
+                if (g0 != kNoLog && g1 != kNoLog && (g1 + 65535u - g0) % 65535u == ratio) atomicMin(&s_found, i);
+            }
+            __syncthreads();
+            if (s_found < A.N) result = int32_t(s_found);
+        }
+    }
+    if (tid == 0) A.located[b] = result;
+}
+
+// One thread per pack; blockIdx.y = group of rows_per_group selected rows,
+// blockIdx.z = stripe.  The stripe's result, row numbers, logs and tables are
+// wave-uniform.  Stripes without a candidate leave at once.
+__global__ __launch_bounds__(256) void k_locate_confirm(const LocateArgs A) {
+    const uint64_t b = blockIdx.z;
+    const int32_t loc = __builtin_amdgcn_readfirstlane(A.located[b]);
+    if (loc < 0) return;  // clean, ROWS, unknown, or refuted by another workgroup already
+    const uint32_t pk = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = pk < A.packs;
+    const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
+    const uint8_t *want = A.want + b * A.want_bstride, *have = A.have + b * A.have_bstride;
+    const ConstWords logs = const_words(A.logs), lut = const_words(A.lut), rows = const_words(A.rows);
+    auto log_of = [&](uint32_t j) {
+        const uint32_t e = j * A.N + uint32_t(loc);
+        return __builtin_amdgcn_readfirstlane((logs[e >> 1] >> ((e & 1u) * 16u)) & 0xFFFFu);
+    };
+    const uint32_t j0 = A.rows ? rows[0] : 0u;
+    // e = D_j0 / G[j0][i], once per workgroup; the log is not the sentinel: k_locate_find took i
+    // from a ratio of two logs
+    const uint32_t inv0 = (65535u - log_of(j0)) % 65535u;
+    uint32_t el = 0, eh = 0;
+    {
+        uint32_t t[kTableWords], l0 = 0, h0 = 0;
+#pragma unroll
+        for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(inv0) * kTableWords + w];
+        if (ok) ld_syndrome(A, want, have, j0, io, l0, h0);
+        gf_muladd4(el, eh, l0, h0, t);
+    }
+
+    const uint32_t r0 = blockIdx.y * A.rows_per_group;
+    const uint32_t r1 = r0 + A.rows_per_group < A.nsel ? r0 + A.rows_per_group : A.nsel;
+    bool refuted = false;
+    for (uint32_t r = r0 ? r0 : 1u; r < r1; ++r) {  // entry 0 is row j0 itself
+        const uint32_t j = A.rows ? rows[r] : r;
+        const uint32_t lg = log_of(j);
+        uint32_t dl = 0, dh = 0;
+        if (ok) ld_syndrome(A, want, have, j, io, dl, dh);
+        // D_j against e * G[j][i]; a zero coefficient (the sentinel) makes the product zero
+        uint32_t pl = 0, ph = 0;
+        if (lg != kNoLog) {
+            uint32_t t[kTableWords];
+#pragma unroll
+            for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(lg) * kTableWords + w];
+            gf_muladd4(pl, ph, el, eh, t);
+        }
+        refuted |= pl != dl || ph != dh;
+    }
+    if (refuted) A.located[b] = kLocateUnknown;  // every refuting lane stores the same word
+}
+
+}  // namespace
+
+hipError_t launch_locate_unit(uint8_t *unit, uint64_t stride, uint32_t i0, uint32_t count, hipStream_t s) {
+    if (!count) return hipSuccess;
+    k_coef_unit_slab<<<dim3((count + 255) / 256), 256, 0, s>>>(unit, stride, i0, count);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_coef_unit_slab");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_log(const uint8_t *coef, uint64_t stride, uint32_t rows, uint32_t i0, uint32_t count,
+                             uint32_t pitch, const uint16_t *log_table, uint16_t *logs, hipStream_t s) {
+    if (!count || !rows) return hipSuccess;
+    if (rows > 65535 || uint64_t(i0) + count > pitch) return hipErrorInvalidValue;
+    k_coef_log_slab<<<dim3((count + 63) / 64, rows), 64, 0, s>>>(coef, stride, rows, i0, count, pitch, log_table, logs);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_coef_log_slab");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_find(const LocateArgs &A, hipStream_t s) {
+    if (!A.stripes) return hipSuccess;
+    if (A.nsel < 2 || A.nsel > A.M || !A.packs || !A.N) return hipErrorInvalidValue;
+    k_locate_find<<<dim3(A.stripes), kFindThreads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_find");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_confirm(const LocateArgs &A0, hipStream_t s) {
+    if (!A0.stripes) return hipSuccess;
+    if (A0.nsel < 2 || !A0.packs || A0.stripes > 65535) return hipErrorInvalidValue;
+    LocateArgs A = A0;
+    const uint32_t threads = A.packs >= 256 ? 256u : (A.packs + 63u) / 64u * 64u, tiles = (A.packs + threads - 1) / threads;
+    // as launch_update: about 1024 workgroups where the call has that many rows,
+    // so that the stripes without a candidate cost few of them
+    const uint64_t units = uint64_t(A.nsel) * tiles * A.stripes;
+    A.rows_per_group = uint32_t(units / 1024 < 1 ? 1 : units / 1024 > 16 ? 16 : units / 1024);
+    const dim3 grid(tiles, (A.nsel + A.rows_per_group - 1) / A.rows_per_group, A.stripes);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    k_locate_confirm<<<grid, threads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_confirm");
+    return hipGetLastError();
+}
+
+}  // namespace rs

@@ -120,6 +120,9 @@ _sig("rs_verify_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64
 _sig("rs_verify_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, _vp, _vp, _E)
 _sig("rs_verify_set_fused", _int, _vp, _int)
+_sig("rs_locate_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, _vp, _vp, _vp, _E)
+_sig("rs_locate_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     ctypes.c_char_p, _vp, _vp, _vp, _E)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -1138,6 +1141,84 @@ def verify_set_fused(mode: int, ctx: Optional[Context] = None) -> None:
     ctx = ctx or default_context()
     if _lib.rs_verify_set_fused(ctx.handle, int(mode)) != 0:
         raise ValueError("invalid argument (rs_status 101)")
+
+
+LOCATE_CLEAN = -1    # RS_LOCATE_CLEAN (include/rs_mi355x.h)
+LOCATE_ROWS = -2     # RS_LOCATE_ROWS
+LOCATE_UNKNOWN = -3  # RS_LOCATE_UNKNOWN
+
+
+def _check_located(d_located, shape, like):
+    """The result tensor of a locate: the caller's (int32, on the device, contiguous, exactly
+    `shape`) or a new one on the device of `like`."""
+    if d_located is None:
+        if not hasattr(like, "data_ptr"):
+            raise ValueError("d_located: needed when the matrices are raw pointers")
+        import torch
+        return torch.empty(shape, dtype=torch.int32, device=like.device)
+    if hasattr(d_located, "data_ptr"):
+        if str(d_located.dtype) != "torch.int32":
+            raise ValueError(f"d_located: dtype must be int32, got {d_located.dtype}")
+        if not d_located.is_cuda:
+            raise ValueError("d_located: must be a device (cuda/HIP) tensor")
+        if tuple(d_located.shape) != tuple(shape) or not d_located.is_contiguous():
+            raise ValueError(f"d_located: expected a contiguous tensor of shape {tuple(shape)}, "
+                             f"got {tuple(d_located.shape)}")
+    return d_located
+
+
+def _locate_mask(recovery_rows, recovery_count):
+    rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
+                                                          "recovery_rows")
+    if recovery_count < 2 or (rows is not None and sum(1 for b in rows if b) < 2):
+        raise ValueError("recovery_rows: a locate needs two recovery rows at least (verify_device takes fewer)")
+    return rows
+
+
+def locate_device(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                  recovery_rows=None, d_located=None, d_mismatch=None, stream=None, rate_: int = RATE_DEFAULT,
+                  ctx: Optional[Context] = None):
+    """verify_device that also names the one corrupt original (rs_locate_device).  Returns
+    (located, mismatch): an int32 tensor [1] holding LOCATE_CLEAN (no selected row differs),
+    LOCATE_ROWS (some differ, some agree: see the flags), the index of the single original that
+    explains every selected row's difference, or LOCATE_UNKNOWN (every row differs and no single
+    original explains it); and verify_device's flag tensor [recovery_count].  recovery_rows must
+    select two rows at least, better three.  Asynchronous on `stream`."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows = _locate_mask(recovery_rows, recovery_count)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    d_located = _check_located(d_located, (1,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_locate_device(ctx.handle, rate_, original_count, recovery_count, shard_bytes, _ptr(d_original),
+                                 _row_stride(d_original), _ptr(d_recovery), _row_stride(d_recovery), rows,
+                                 _ptr(d_located), _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch
+
+
+def locate_device_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                        recovery_rows=None, d_located=None, d_mismatch=None, stream=None, rate_: int = RATE_DEFAULT,
+                        ctx: Optional[Context] = None):
+    """locate_device on a batch of stripes sharing ONE row mask (rs_locate_device_batch); tensors
+    [stripes, rows, shard_bytes].  Returns (located [stripes], mismatch [stripes, recovery_count])."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows = _locate_mask(recovery_rows, recovery_count)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_locate_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                       d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows,
+                                       _ptr(d_located), _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch
 
 
 class DeviceCall:
