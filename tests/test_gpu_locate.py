@@ -14,6 +14,7 @@ import pytest
 
 import locate_model as LM
 import oracle_lib as O
+import span_cases as SC
 import test_gpu_verify as V
 
 pytestmark = pytest.mark.gpu
@@ -183,11 +184,57 @@ def masks_of(M):
 
 @pytest.mark.parametrize("rate,N,M,S,pad", [("high", 70, 100, 64, 0), ("default", 300, 500, 72, 8),
                                             ("default", 1024, 1024, 66, 4), ("high", 1000, 100, 66, 0),
-                                            ("default", 4096, 4096, 64, 0)], ids=lambda v: str(v))
+                                            ("default", 4096, 4096, 64, 0)] + [s + (0,) for s in SC.MASK_SHAPES],
+                         ids=lambda v: str(v))
 def test_masks(torch, rs, rate, N, M, S, pad):
     """Each mask over the cases that mean something under it; then junk (0xC3) in the unselected
     rows and in the row padding changes neither output."""
+    check_masks(torch, rs, rate, N, M, S, pad)
+
+
+@pytest.mark.parametrize("rate,N,M,S,mode", SC.MASK_SHAPES_MODE0, ids=lambda v: str(v))
+def test_masks_on_the_pass_kernels(torch, rs, rate, N, M, S, mode):
+    """test_masks with the column kernels off: two pass levels over several chunks."""
+    try:
+        rs.mono_enable(mode)
+        check_masks(torch, rs, rate, N, M, S, 0)
+    finally:
+        rs.mono_enable(True)
+
+
+def check_span_masks(torch, rs, rate, N, M, S, pad):
+    """The spans of tests/span_cases.py as masks (every third row inside a span unselected; the
+    call takes no fewer than two rows), junk that differs in every unselected row: a corrupt
+    original i in {0, N - 1} comes back as i, and the flags are the oracle's -- every selected
+    row, as one corrupt original changes them all."""
     orig, rec = V.stripe(rate, N, M, S)
+    rng = np.random.default_rng(N + 5 * M)
+    for mask in V.span_masks(rate, N, M):
+        sel = mask != 0
+        if int(sel.sum()) < 2:
+            continue
+        junk = rec.copy()
+        junk[~sel] ^= rng.integers(1, 256, (int((~sel).sum()), S), dtype=np.uint8)
+        rows = np.flatnonzero(sel)
+        what = f"{rate} {N}:{M} x {S} pad {pad} span mask [{rows[0]}, {rows[-1] + 1})"
+        got, flags = locate_one(torch, rs, rate, N, M, S, orig, junk, pad, mask, what + " clean")
+        assert got == CLEAN and not flags.any(), (what, got, np.flatnonzero(flags)[:8])
+        for i in sorted({0, N - 1}):
+            bad = orig.copy()
+            bad[i, (7 * i + 3) % S] ^= 0x40
+            enc = O.encode(rate, bad, M)
+            truth = ((enc != junk).any(axis=1) & sel).astype(np.uint8)
+            want, want_flags = LM.locate(rate, bad, junk, mask=mask, D=LM.elements(enc ^ junk).astype(np.int64))
+            assert want == i and np.array_equal(truth, mask), f"{what}: the model says {want} for original {i}"
+            got, flags = locate_one(torch, rs, rate, N, M, S, bad, junk, pad, mask, f"{what} original {i}")
+            assert np.array_equal(flags, truth) and np.array_equal(truth, want_flags), \
+                f"{what}: flagged rows {np.flatnonzero(flags).tolist()[:8]}, want {np.flatnonzero(truth).tolist()[:8]}"
+            assert got == i, f"{what}: located {got}, want {i}"
+
+
+def check_masks(torch, rs, rate, N, M, S, pad):
+    orig, rec = V.stripe(rate, N, M, S)
+    check_span_masks(torch, rs, rate, N, M, S, pad)
     for mask in masks_of(M):
         run_cases(torch, rs, rate, N, M, S, pad, mask=mask,
                   only=("none", "original 0 bit0", f"original {N // 2} shard", f"original {N - 1} lastbit",

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import span_cases as SC
 
 pytestmark = pytest.mark.gpu
 
@@ -205,13 +206,36 @@ def test_padding_is_not_compared(torch, rs, rate, N, M, S, pad, fused):
     assert np.flatnonzero(got).tolist() == [M - 2]
 
 
+def span_masks(rate, N, M):
+    """The spans of tests/span_cases.py (the ends of the matrix, odd rows, the rows around n / 2, a
+    pass level and, for LowRate's output chunks, the chunk boundaries, whole and partial chunks and
+    rows inside them) as masks, every third row inside a span unselected."""
+    forced = rate if rate != "default" else "high" if O.lib().orc_use_high_rate(N, M) == 1 else "low"
+    return [SC.span_mask(M, lo, hi) for _, lo, hi in SC.spans(forced, N, M)]
+
+
 @pytest.mark.parametrize("fused", [1, 0])
 @pytest.mark.parametrize("rate,N,M,S", [("high", 70, 100, 64), ("default", 300, 500, 72), ("high", 1000, 100, 66),
-                                        ("default", 4096, 4096, 64)], ids=lambda v: str(v))
+                                        ("default", 4096, 4096, 64)] + SC.MASK_SHAPES, ids=lambda v: str(v))
 def test_masks(torch, rs, rate, N, M, S, fused):
     """Unselected rows hold junk that differs and stay 0; the selected rows are right, those of a
     narrowed span with unselected rows inside it included; a mask that selects nothing gives
     all-zero flags and launches no kernel."""
+    check_masks(torch, rs, rate, N, M, S, fused)
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("rate,N,M,S,mode", SC.MASK_SHAPES_MODE0, ids=lambda v: str(v))
+def test_masks_on_the_pass_kernels(torch, rs, rate, N, M, S, mode, fused):
+    """test_masks with the column kernels off: two pass levels over several chunks."""
+    try:
+        rs.mono_enable(mode)
+        check_masks(torch, rs, rate, N, M, S, fused)
+    finally:
+        rs.mono_enable(True)
+
+
+def check_masks(torch, rs, rate, N, M, S, fused):
     orig, rec = stripe(rate, N, M, S)
     rng = np.random.default_rng(M)
     rs.verify_set_fused(fused)
@@ -222,7 +246,8 @@ def test_masks(torch, rs, rate, N, M, S, fused):
     one[M - 1] = 1
     most = np.ones(M, np.uint8)
     most[1::3] = 0
-    for mask in (span, one, most, np.ones(M, np.uint8), span):  # (the last: the mask changes back)
+    # (the second `span`: the mask changes back)
+    for mask in [span, one, most, np.ones(M, np.uint8), span] + span_masks(rate, N, M):
         sel = np.flatnonzero(mask)
         clean = rec.copy()  # the selected rows right, junk in the others
         clean[mask == 0] = rng.integers(0, 256, (int((mask == 0).sum()), S), dtype=np.uint8)
