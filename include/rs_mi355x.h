@@ -40,6 +40,8 @@
  *   originals
  *   rs_locate_device (+ _batch): the verify that also names the one corrupt
  *   original of a stripe whose recovery shards all disagree
+ *   rs_heal_device (+ _batch): the locate that also writes the correction, to the
+ *   located original or to the differing recovery rows, with no host round trip
  *
  * Thread-safety: a context may be shared by threads (like DefaultEngine:
  * Send + Sync, src/lib.rs:385-409): calls on one context are serialized on the
@@ -636,8 +638,8 @@ rs_status rs_verify_set_fused(rs_context *ctx, int mode);
  * "Locate" has the rest.
  *   Not covered: one corrupt original together with corrupt recovery rows
  * (majority logic over row subsets); a mask per stripe; stripes with missing
- * originals; writing the correction e back; the host pipeline, the object API and
- * the sharded classes; a fused form on k_mono_verify. */
+ * originals; the host pipeline, the object API and the sharded classes; a fused
+ * form on k_mono_verify.  (Writing the correction back: rs_heal_device below.) */
 #define RS_LOCATE_CLEAN (-1)
 #define RS_LOCATE_ROWS (-2)
 #define RS_LOCATE_UNKNOWN (-3)
@@ -653,6 +655,105 @@ rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  uint64_t recovery_stride, uint64_t recovery_stripe_stride,
                                  const uint8_t *recovery_check, int32_t *d_located, uint8_t *d_mismatch, void *stream,
                                  rs_error *err);
+
+/* ---- heal: fix what the locate found, in place, on the device ----
+ * A scrub built from the calls above is three calls with a host round trip in the
+ * middle: rs_locate_device_batch, a synchronize and a read of d_located and the
+ * flags, then rs_repair_device_batch_masks, a full decode of every damaged stripe.
+ * Yet at the end of the locate everything a heal needs is on the device: for a
+ * located original i the confirm has just formed e = D_j0 / G[j0][i] (j0: the first
+ * selected row) in every column, and the clean shard is original_i ^ e; for a
+ * RS_LOCATE_ROWS stripe the clean recovery rows are the encode of the stored
+ * originals, still in the per-stream scratch.  This call is the locate followed by
+ * one more launch per group of stripes that writes those: asynchronous on
+ * `stream`, no host synchronization, no masks per stripe, no decode.
+ *   Arguments, strides (0 = dense), alignment rules, the byte-wise path, the block
+ * and tail layout and the HOST mask recovery_check (NULL = every row; ONE mask for
+ * every stripe) are those of rs_locate_device[_batch]; rows marked 0 are never
+ * read and never written.  d_original and d_recovery are written in place.
+ * mode: RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY, at least one.  d_action: DEVICE
+ * array of one byte per stripe.
+ *   Result.  d_located and d_mismatch hold exactly what rs_locate_device_batch
+ * writes for the same arguments: they describe the stripe AS FOUND, before
+ * anything is healed (a caller logs them).  Every byte of d_action is defined:
+ *   RS_HEAL_ORIGINAL  d_located[b] = i >= 0 and mode has the bit: original i of
+ *                     stripe b has become original_i ^ e, e = D_j0 / G[j0][i] per
+ *                     column.  Only its shard_bytes bytes are written, not the row
+ *                     padding.  The confirm has shown D_j = G[j][i] * e for every
+ *                     selected row, so every selected row now agrees; and when
+ *                     original i alone was corrupt the row is byte-identical to
+ *                     the clean shard, since G[j0][i] != 0 makes e unique.
+ *   RS_HEAL_RECOVERY  d_located[b] = RS_LOCATE_ROWS, mode has the bit, and at most
+ *                     max_rows selected rows differ: each differing selected row
+ *                     of d_recovery has become the encode of the stored originals
+ *                     (shard_bytes bytes each; rows that agree, unselected rows
+ *                     and padding are not written).  max_rows is the caller's
+ *                     majority threshold; 0 never rewrites.
+ *   0                 the stripe is untouched: CLEAN, UNKNOWN, ROWS above the
+ *                     threshold, or an outcome whose mode bit is off.
+ * Nothing else is written anywhere.  A second heal of a healed stripe reports
+ * RS_LOCATE_CLEAN with action 0.
+ *   CAVEAT (the locate's "NOT proven", carried over): a ROWS stripe does not prove
+ * the originals intact.  RS_HEAL_RECOVERY can make recovery rows consistent with
+ * CORRUPT originals -- after which a verify says clean and the damage can no
+ * longer be found.  max_rows and the choice to set the bit belong to the caller:
+ * keep max_rows well below half of the selected rows, so that the agreeing rows
+ * outvote the rewritten ones.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * d_recovery, d_located, d_mismatch or d_action -> RS_ERR_INVALID_ARGUMENT;
+ * rs_validate; the two row strides; mode == 0 or a bit outside the two ->
+ * RS_ERR_INVALID_ARGUMENT (rs_locate_device is the call for mode 0); fewer than 2
+ * selected rows, or fewer than 3 with RS_HEAL_ORIGINAL -> RS_ERR_INVALID_ARGUMENT
+ * (with two rows, two corrupt originals can be attributed to a third, see above;
+ * this call writes on that evidence, so it takes three); the locate's shape bound.
+ * stripes == 0: RS_OK, nothing launched or written, the context not touched.  The
+ * matrices must not overlap one another or the three outputs.
+ *   Launches: the locate's, group of stripes by group of stripes, its coefficient
+ * table shared with it (a locate after a heal on the stream finds the table, and
+ * the reverse); k_locate_find also stores each stripe's count of differing rows
+ * into per-stream scratch; and one k_heal per group directly after that group's
+ * k_locate_confirm, while the group's encode is still in scratch (off the column
+ * kernel a group is one stripe and the scratch is reused).  k_heal has the
+ * confirm's grid; workgroups of a stripe with nothing to do leave at once.
+ *   Measured (tools/heal_time.py, profiles/heal/heal_time.txt; 1024:1024, every
+ * row, both mode bits, max_rows 16, us per call, the legs interleaved in one
+ * session; locate = rs_locate_device_batch on the clean batch, whose kernels are
+ * the parent commit's, spread = max - min of its five rounds; original / row = one
+ * corrupt original / one corrupt recovery row in EVERY stripe; scrub = the three
+ * calls with their synchronize, host read and masks; the four damaged legs net
+ * of the 4.3-4.5 us launch that puts the damage back before each call; in
+ * brackets the ratio to the locate):
+ *     shape               locate spread  heal clean    heal original heal row      scrub original scrub row
+ *     1 KiB, one stripe    15.50   0.77  18.10 (1.17)  21.26 (1.37)  18.71 (1.21)   98.4 (6.35)    89.6 (5.78)
+ *     1 KiB, 64 stripes   241.0    1.33  244.0 (1.01)  272.1 (1.13)  247.3 (1.03)  987.4 (4.10)   996.9 (4.14)
+ *     64 KiB, one stripe  125.0    5.53  128.6 (1.03)  169.9 (1.36)  132.1 (1.06)  399.7 (3.20)   275.0 (2.20)
+ * A clean heal costs the locate plus one small launch, as expected: +2.6 / +3.0 /
+ * +3.6 us, k_heal at the 6.1-6.3 us floor between two of the library's events
+ * (at the single 1 KiB stripe the leg's own rounds spread 3.3 us, more than the
+ * difference).  A healed ROW costs 3.2 / 6.3 / 7.0 us over the locate: k_heal's
+ * copy is 8.6-9.2 us by the events.  A healed ORIGINAL costs 5.8 / 31.1 / 44.9 us
+ * over the CLEAN locate, but that is the locate's own corrupt case (the find's
+ * candidate path and the confirm: +7.2 / +25.7 / +37.6 us when it was measured
+ * alone, above) plus the k_heal launch, which stays at 6.4-6.8 us: one row read
+ * and written.  Both beat the three-call scrub by more than its decode's time
+ * (k_mono_repair_masks 20-22 / 589-617 us, the 64 KiB decode's passes 164 /
+ * 103 us by the events): by 77 / 715 / 230 us for an original and 71 / 750 /
+ * 143 us for a row, the rest being the synchronize, the two reads on the host and
+ * the masks.  DESIGN.md "Heal" has the rest.
+ *   Not covered: a mask per stripe; stripes with missing originals; the host
+ * pipeline, the object API and the sharded classes. */
+#define RS_HEAL_ORIGINAL 1u /* a located original i: original_i ^= e */
+#define RS_HEAL_RECOVERY 2u /* a ROWS stripe: rewrite its differing selected rows */
+rs_status rs_heal_device(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                         uint64_t shard_bytes, void *d_original, uint64_t original_stride, void *d_recovery,
+                         uint64_t recovery_stride, const uint8_t *recovery_check, uint32_t mode, uint32_t max_rows,
+                         int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action, void *stream, rs_error *err);
+rs_status rs_heal_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                               uint64_t shard_bytes, uint64_t stripes, void *d_original, uint64_t original_stride,
+                               uint64_t original_stripe_stride, void *d_recovery, uint64_t recovery_stride,
+                               uint64_t recovery_stripe_stride, const uint8_t *recovery_check, uint32_t mode,
+                               uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action,
+                               void *stream, rs_error *err);
 
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x

@@ -185,6 +185,7 @@ struct VerifyWs {
 // the verify's, VerifyWs.)
 struct LocateWs {
     DevBuf unit, coef, logs;
+    DevBuf differ;  // rs_heal_device*: a group's counts of differing rows, one word per stripe
     bool valid = false;  // `logs` holds the table of (high, n, m)
     int high = 0;
     uint64_t n = 0, m = 0;
@@ -2036,10 +2037,20 @@ struct LocateCall : VerifyCall {
     int32_t *d_located;  // one per stripe
 };
 
+// What rs_heal_device* adds to a locate (DESIGN.md "Heal"): the two matrices
+// writable, the mode bits, the threshold, one action byte per stripe.
+struct HealCall {
+    uint8_t *d_orig, *d_rec;
+    uint32_t mode, max_rows;
+    uint8_t *d_action;
+};
+
 // The caller has checked that the mask selects two rows at least, the shape bound
 // and that stripes > 0.  The unfused verify (verify_dev) with two more launches per
-// group of stripes while the encode is still in scratch.
-void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V, hipStream_t s) {
+// group of stripes while the encode is still in scratch.  With a heal, k_heal is a
+// third, inside the loop: off the column kernel the scratch holds one stripe at a time.
+void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V, hipStream_t s,
+                const HealCall *H = nullptr) {
     const uint32_t M = uint32_t(V.M);
     uint32_t lo = 0, hi = M, nsel = M;
     if (V.mask) {
@@ -2064,6 +2075,8 @@ void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
     ge.rec_stride = W;
     ge.orig_bstride = V.orig_bstride;
     ge.rec_bstride = V.M * W;
+    uint32_t *differ = nullptr;
+    if (H) differ = static_cast<uint32_t *>(ws.loc->differ.get(std::min<uint64_t>(group, V.stripes) * 4));
     for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
         ge.stripes = uint32_t(std::min<uint64_t>(group, V.stripes - b0));
         const uint8_t *o = V.d_orig + b0 * V.orig_bstride;
@@ -2076,7 +2089,7 @@ void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
         R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
         R.fmt = g.fmt;
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(R, s); });
-        rs::LocateArgs A;
+        rs::HealArgs A;  // the locate's kernels take its LocateArgs
         A.want = R.want, A.want_stride = W, A.want_bstride = R.want_bstride;
         A.have = R.have, A.have_stride = R.have_stride, A.have_bstride = R.have_bstride;
         A.rows = d_list, A.nsel = nsel, A.packs = g.packs, A.stripes = ge.stripes;
@@ -2087,8 +2100,17 @@ void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
         A.fmt = g.fmt;
         // find: the flags and one word per stripe; a stripe with a candidate reads up to
         // two rows and two table rows more.  confirm: as the compare, where it runs at all
+        A.differ = differ;
         update_launch(s, (V.M + 4) * uint64_t(ge.stripes), [&] { return rs::launch_locate_find(A, s); });
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_locate_confirm(A, s); });
+        if (!H) continue;
+        A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
+        A.rec = H->d_rec + b0 * V.rec_bstride;
+        A.mode = H->mode, A.max_rows = H->max_rows;
+        A.action = H->d_action + b0;
+        // a stripe with nothing to heal costs a word; a located one three rows, a ROWS one
+        // two per rewritten row
+        update_launch(s, 5 * uint64_t(ge.stripes), [&] { return rs::launch_heal(A, s); });
     }
 }
 
@@ -3137,6 +3159,57 @@ rs_status rs_locate_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M
                            rs_error *err) {
     return rs_locate_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
                                   d_located, d_mismatch, stream, err);
+}
+
+// ---- heal: the locate that also writes the correction (include/rs_mi355x.h) ----
+
+rs_status rs_heal_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, uint64_t stripes,
+                               void *d_orig, uint64_t orig_stride, uint64_t orig_stripe_stride, void *d_rec,
+                               uint64_t rec_stride, uint64_t rec_stripe_stride, const uint8_t *recovery_check,
+                               uint32_t mode, uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch,
+                               uint8_t *d_action, void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_located) || !ptr_ok(d_mismatch) || !ptr_ok(d_action))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    uint64_t nsel = M;
+    if (recovery_check) {
+        nsel = 0;
+        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
+    }
+    // the locate's two rows; three to write an original on the evidence (with two, two
+    // corrupt originals can be attributed to a third)
+    if (nsel < ((mode & RS_HEAL_ORIGINAL) ? 3u : 2u)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                      0, 0, recovery_check, d_mismatch},
+                     d_located};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        locate_dev(ctx, sw.w, high != 0, g, V, s, &H);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_heal_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, void *d_orig,
+                         uint64_t orig_stride, void *d_rec, uint64_t rec_stride, const uint8_t *recovery_check,
+                         uint32_t mode, uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action,
+                         void *stream, rs_error *err) {
+    return rs_heal_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
+                                mode, max_rows, d_located, d_mismatch, d_action, stream, err);
 }
 
 // ---- encoder ----------------------------------------------------------------

@@ -510,9 +510,26 @@ struct LocateArgs {
     const uint16_t *log_table = nullptr;  // log of every element (rs_context::d_log)
     const uint32_t *lut = nullptr;        // perm tables by log factor (rs_context::d_lut)
     ShardFormat fmt;
+    uint32_t *differ = nullptr;  // a heal's: the find stores stripe b's count of differing selected rows
 };
 hipError_t launch_locate_find(const LocateArgs &A, hipStream_t stream);
 hipError_t launch_locate_confirm(const LocateArgs &A, hipStream_t stream);
+
+// ---- heal (rs_heal_device*, rs_locate.hip; DESIGN.md "Heal") -----------------
+// After the find (with `differ`) and the confirm of the same LocateArgs, while the
+// encode is still in `want`.  launch_heal (the confirm's grid) writes every
+// action[b] and, where action[b] != 0, the stripe: kHealOriginal (located[b] = i >= 0
+// and the mode bit): original i ^= D_j0 / G[j0][i] over every pack; kHealRecovery
+// (located[b] = kLocateRows, the mode bit, differ[b] <= max_rows): every flagged
+// selected row of `rec` = that row of `want`.  rec is the matrix `have` names.
+constexpr uint32_t kHealOriginal = 1, kHealRecovery = 2;
+struct HealArgs : LocateArgs {
+    uint8_t *orig = nullptr, *rec = nullptr;
+    uint64_t orig_stride = 0, orig_bstride = 0;
+    uint32_t mode = 0, max_rows = 0;
+    uint8_t *action = nullptr;  // one byte per stripe
+};
+hipError_t launch_heal(const HealArgs &A, hipStream_t stream);
 
 // x[rows] *= exp(log_m) over `blocks` 64-byte blocks.
 hipError_t launch_mul(uint8_t *rows, uint64_t blocks, const uint32_t *lut_entry, hipStream_t stream);

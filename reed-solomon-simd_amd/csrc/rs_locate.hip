@@ -15,6 +15,14 @@
 //   k_locate_confirm   D_j == (D_j0 / G[j0][i]) * G[j][i] over every selected row and
 //                      pack of the stripes that name an i; a refutation stores
 //                      RS_LOCATE_UNKNOWN
+//
+// and of a heal (rs_heal_device*, DESIGN.md "Heal"), after the confirm and while
+// the encode is still in scratch:
+//
+//   k_heal             a located original i: original_i ^= D_j0 / G[j0][i] (the
+//                      confirm's e, recomputed); a ROWS stripe within the caller's
+//                      threshold: its flagged selected rows copied from the scratch;
+//                      one action byte per stripe
 #include <cstdio>
 
 #include "rs_device.hpp"
@@ -75,6 +83,7 @@ __global__ __launch_bounds__(kFindThreads) void k_locate_find(const LocateArgs A
     if (c) atomicAdd(&s_count, c);
     __syncthreads();
     const uint32_t differ = s_count;
+    if (A.differ && tid == 0) A.differ[b] = differ;
     if (differ < A.nsel) {  // most stripes of a scrub end here
         if (tid == 0) A.located[b] = differ ? kLocateRows : kLocateClean;
         return;
@@ -122,6 +131,26 @@ __global__ __launch_bounds__(kFindThreads) void k_locate_find(const LocateArgs A
     if (tid == 0) A.located[b] = result;
 }
 
+// log G[j][loc] from the table, wave-uniform (j and loc are).
+__device__ __forceinline__ uint32_t coef_log(ConstWords logs, uint32_t N, uint32_t j, uint32_t loc) {
+    const uint32_t e = j * N + loc;
+    return __builtin_amdgcn_readfirstlane((logs[e >> 1] >> ((e & 1u) * 16u)) & 0xFFFFu);
+}
+
+// e = D_j0 / G[j0][loc] of pack io (zero where !ok); the log is not the sentinel:
+// k_locate_find took loc from a ratio of two logs
+__device__ __forceinline__ void locate_error(const LocateArgs &A, ConstWords logs, ConstWords lut, uint32_t j0,
+                                             uint32_t loc, const uint8_t *want, const uint8_t *have, const PackIO &io,
+                                             bool ok, uint32_t &el, uint32_t &eh) {
+    const uint32_t inv0 = (65535u - coef_log(logs, A.N, j0, loc)) % 65535u;
+    uint32_t t[kTableWords], l0 = 0, h0 = 0;
+#pragma unroll
+    for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(inv0) * kTableWords + w];
+    if (ok) ld_syndrome(A, want, have, j0, io, l0, h0);
+    el = 0, eh = 0;
+    gf_muladd4(el, eh, l0, h0, t);
+}
+
 // One thread per pack; blockIdx.y = group of rows_per_group selected rows,
 // blockIdx.z = stripe.  The stripe's result, row numbers, logs and tables are
 // wave-uniform.  Stripes without a candidate leave at once.
@@ -134,22 +163,10 @@ __global__ __launch_bounds__(256) void k_locate_confirm(const LocateArgs A) {
     const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
     const uint8_t *want = A.want + b * A.want_bstride, *have = A.have + b * A.have_bstride;
     const ConstWords logs = const_words(A.logs), lut = const_words(A.lut), rows = const_words(A.rows);
-    auto log_of = [&](uint32_t j) {
-        const uint32_t e = j * A.N + uint32_t(loc);
-        return __builtin_amdgcn_readfirstlane((logs[e >> 1] >> ((e & 1u) * 16u)) & 0xFFFFu);
-    };
+    auto log_of = [&](uint32_t j) { return coef_log(logs, A.N, j, uint32_t(loc)); };
     const uint32_t j0 = A.rows ? rows[0] : 0u;
-    // e = D_j0 / G[j0][i], once per workgroup; the log is not the sentinel: k_locate_find took i
-    // from a ratio of two logs
-    const uint32_t inv0 = (65535u - log_of(j0)) % 65535u;
-    uint32_t el = 0, eh = 0;
-    {
-        uint32_t t[kTableWords], l0 = 0, h0 = 0;
-#pragma unroll
-        for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(inv0) * kTableWords + w];
-        if (ok) ld_syndrome(A, want, have, j0, io, l0, h0);
-        gf_muladd4(el, eh, l0, h0, t);
-    }
+    uint32_t el, eh;  // e = D_j0 / G[j0][i], once per workgroup
+    locate_error(A, logs, lut, j0, uint32_t(loc), want, have, io, ok, el, eh);
 
     const uint32_t r0 = blockIdx.y * A.rows_per_group;
     const uint32_t r1 = r0 + A.rows_per_group < A.nsel ? r0 + A.rows_per_group : A.nsel;
@@ -170,6 +187,49 @@ __global__ __launch_bounds__(256) void k_locate_confirm(const LocateArgs A) {
         refuted |= pl != dl || ph != dh;
     }
     if (refuted) A.located[b] = kLocateUnknown;  // every refuting lane stores the same word
+}
+
+// The confirm's grid.  Every branch but the pack bound is uniform over the
+// workgroup; a stripe with nothing to heal (the common one of a scrub) leaves at once.
+__global__ __launch_bounds__(256) void k_heal(const HealArgs A) {
+    const uint64_t b = blockIdx.z;
+    const int32_t loc = __builtin_amdgcn_readfirstlane(A.located[b]);
+    uint32_t action = 0;
+    if (loc >= 0) {
+        if (A.mode & kHealOriginal) action = kHealOriginal;
+    } else if (loc == kLocateRows && (A.mode & kHealRecovery)) {
+        if (uint32_t(__builtin_amdgcn_readfirstlane(A.differ[b])) <= A.max_rows) action = kHealRecovery;
+    }
+    if ((blockIdx.x | blockIdx.y | threadIdx.x) == 0) A.action[b] = uint8_t(action);
+    if (!action) return;
+    const uint32_t pk = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = pk < A.packs;
+    const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
+    const uint8_t *want = A.want + b * A.want_bstride;
+    const ConstWords rows = const_words(A.rows);
+    if (action == kHealOriginal) {
+        if (blockIdx.y) return;  // one row to write: row group 0 does it
+        uint32_t el, eh;
+        locate_error(A, const_words(A.logs), const_words(A.lut), A.rows ? rows[0] : 0u, uint32_t(loc), want,
+                     A.have + b * A.have_bstride, io, ok, el, eh);
+        if (!ok) return;
+        uint8_t *p = A.orig + b * A.orig_bstride + uint64_t(loc) * A.orig_stride + io.lo;
+        st_word(p, ld_word(p, io) ^ el, io);
+        st_word(p + io.hi_delta, ld_word(p + io.hi_delta, io) ^ eh, io);
+        return;
+    }
+    const uint8_t *flags = A.flags + b * A.flag_bstride;
+    uint8_t *rec = A.rec + b * A.have_bstride;
+    const uint32_t r0 = blockIdx.y * A.rows_per_group;
+    const uint32_t r1 = r0 + A.rows_per_group < A.nsel ? r0 + A.rows_per_group : A.nsel;
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t j = A.rows ? rows[r] : r;
+        if (!__builtin_amdgcn_readfirstlane(uint32_t(flags[j])) || !ok) continue;
+        const uint8_t *w = want + uint64_t(j) * A.want_stride + io.lo;
+        uint8_t *h = rec + uint64_t(j) * A.have_stride + io.lo;
+        st_word(h, ld_word(w, io), io);
+        st_word(h + io.hi_delta, ld_word(w + io.hi_delta, io), io);
+    }
 }
 
 }  // namespace
@@ -211,6 +271,23 @@ hipError_t launch_locate_confirm(const LocateArgs &A0, hipStream_t s) {
     if (grid.y > 65535) return hipErrorInvalidValue;
     k_locate_confirm<<<grid, threads, 0, s>>>(A);
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_confirm");
+    return hipGetLastError();
+}
+
+hipError_t launch_heal(const HealArgs &A0, hipStream_t s) {
+    if (!A0.stripes) return hipSuccess;
+    if (A0.nsel < 2 || !A0.packs || A0.stripes > 65535 || !A0.differ || !A0.action || !A0.orig || !A0.rec ||
+        !A0.mode || (A0.mode & ~(kHealOriginal | kHealRecovery)))
+        return hipErrorInvalidValue;
+    HealArgs A = A0;
+    // the confirm's grid (launch_locate_confirm)
+    const uint32_t threads = A.packs >= 256 ? 256u : (A.packs + 63u) / 64u * 64u, tiles = (A.packs + threads - 1) / threads;
+    const uint64_t units = uint64_t(A.nsel) * tiles * A.stripes;
+    A.rows_per_group = uint32_t(units / 1024 < 1 ? 1 : units / 1024 > 16 ? 16 : units / 1024);
+    const dim3 grid(tiles, (A.nsel + A.rows_per_group - 1) / A.rows_per_group, A.stripes);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    k_heal<<<grid, threads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_heal");
     return hipGetLastError();
 }
 

@@ -123,6 +123,10 @@ _sig("rs_verify_set_fused", _int, _vp, _int)
 _sig("rs_locate_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, _vp, _vp, _vp, _E)
 _sig("rs_locate_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, _vp, _vp, _vp, _E)
+_sig("rs_heal_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, ctypes.c_uint32,
+     ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
+_sig("rs_heal_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -1219,6 +1223,95 @@ def locate_device_batch(original_count: int, recovery_count: int, shard_bytes: i
                                        d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows,
                                        _ptr(d_located), _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
     return d_located, d_mismatch
+
+
+HEAL_ORIGINAL = 1  # RS_HEAL_ORIGINAL (include/rs_mi355x.h)
+HEAL_RECOVERY = 2  # RS_HEAL_RECOVERY
+
+
+def _check_action(d_action, shape, like):
+    """The action tensor of a heal: the caller's (uint8, on the device, contiguous, exactly
+    `shape`) or a new one on the device of `like`."""
+    if d_action is None:
+        if not hasattr(like, "data_ptr"):
+            raise ValueError("d_action: needed when the matrices are raw pointers")
+        import torch
+        return torch.empty(shape, dtype=torch.uint8, device=like.device)
+    if hasattr(d_action, "data_ptr"):
+        if str(d_action.dtype) != "torch.uint8":
+            raise ValueError(f"d_action: dtype must be uint8, got {d_action.dtype}")
+        if not d_action.is_cuda:
+            raise ValueError("d_action: must be a device (cuda/HIP) tensor")
+        if tuple(d_action.shape) != tuple(shape) or not d_action.is_contiguous():
+            raise ValueError(f"d_action: expected a contiguous tensor of shape {tuple(shape)}, "
+                             f"got {tuple(d_action.shape)}")
+    return d_action
+
+
+def _heal_args(recovery_rows, recovery_count, mode, max_rows):
+    mode, max_rows = int(mode), int(max_rows)
+    if mode == 0 or mode & ~(HEAL_ORIGINAL | HEAL_RECOVERY):
+        raise ValueError(f"mode: HEAL_ORIGINAL | HEAL_RECOVERY, at least one (locate_device takes none), got {mode}")
+    if not 0 <= max_rows < 1 << 32:
+        raise ValueError(f"max_rows: 0 .. 2^32 - 1, got {max_rows}")
+    rows = _locate_mask(recovery_rows, recovery_count)
+    if mode & HEAL_ORIGINAL and (recovery_count if rows is None else sum(1 for b in rows if b)) < 3:
+        raise ValueError("recovery_rows: HEAL_ORIGINAL writes an original on the rows' evidence and needs three "
+                         "recovery rows at least")
+    return rows, mode, max_rows
+
+
+def heal_device(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                recovery_rows=None, mode: int = HEAL_ORIGINAL, max_rows: int = 0, d_located=None, d_mismatch=None,
+                d_action=None, stream=None, rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """locate_device that also writes the correction, in place (rs_heal_device).  mode &
+    HEAL_ORIGINAL: a located original i becomes original_i ^ e.  mode & HEAL_RECOVERY: the
+    differing selected rows of a LOCATE_ROWS stripe become the encode of the stored originals,
+    when at most max_rows differ -- which does NOT prove those originals intact (the caveat in
+    include/rs_mi355x.h); the bit and the threshold are the caller's choice.  Returns (located,
+    mismatch, action): the locate's report of the stripe as found, and a uint8 tensor [1] holding
+    HEAL_ORIGINAL, HEAL_RECOVERY or 0 (untouched).  Asynchronous on `stream`."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows, mode, max_rows = _heal_args(recovery_rows, recovery_count, mode, max_rows)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    d_located = _check_located(d_located, (1,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    d_action = _check_action(d_action, (1,), d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_heal_device(ctx.handle, rate_, original_count, recovery_count, shard_bytes, _ptr(d_original),
+                               _row_stride(d_original), _ptr(d_recovery), _row_stride(d_recovery), rows, mode,
+                               max_rows, _ptr(d_located), _ptr(d_mismatch), _ptr(d_action), _stream(stream),
+                               ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_action
+
+
+def heal_device_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                      recovery_rows=None, mode: int = HEAL_ORIGINAL, max_rows: int = 0, d_located=None,
+                      d_mismatch=None, d_action=None, stream=None, rate_: int = RATE_DEFAULT,
+                      ctx: Optional[Context] = None):
+    """heal_device on a batch of stripes sharing ONE row mask (rs_heal_device_batch); tensors
+    [stripes, rows, shard_bytes].  Returns (located [stripes], mismatch [stripes, recovery_count],
+    action [stripes])."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows, mode, max_rows = _heal_args(recovery_rows, recovery_count, mode, max_rows)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_action = _check_action(d_action, (n,), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_heal_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                     d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows, mode,
+                                     max_rows, _ptr(d_located), _ptr(d_mismatch), _ptr(d_action), _stream(stream),
+                                     ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_action
 
 
 class DeviceCall:
