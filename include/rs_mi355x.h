@@ -40,6 +40,8 @@
  *   originals
  *   rs_locate_device (+ _batch): the verify that also names the one corrupt
  *   original of a stripe whose recovery shards all disagree
+ *   rs_locate_device_robust (+ _batch): the locate that tolerates, and names, a
+ *   few corrupt recovery shards beside the corrupt original
  *   rs_heal_device (+ _batch): the locate that also writes the correction, to the
  *   located original or to the differing recovery rows, with no host round trip
  *
@@ -636,10 +638,11 @@ rs_status rs_verify_set_fused(rs_context *ctx, int mode);
  * 1 KiB and 14 us at 64 KiB.  The fused verify (10.55 / 240.5 us) stays the
  * cheaper first pass of a scrub that expects no corrupt originals.  DESIGN.md
  * "Locate" has the rest.
- *   Not covered: one corrupt original together with corrupt recovery rows
- * (majority logic over row subsets); a mask per stripe; stripes with missing
+ *   Not covered: a mask per stripe; stripes with missing
  * originals; the host pipeline, the object API and the sharded classes; a fused
- * form on k_mono_verify.  (Writing the correction back: rs_heal_device below.) */
+ * form on k_mono_verify.  (One corrupt original together with corrupt recovery
+ * rows: rs_locate_device_robust below.  Writing the correction back:
+ * rs_heal_device below.) */
 #define RS_LOCATE_CLEAN (-1)
 #define RS_LOCATE_ROWS (-2)
 #define RS_LOCATE_UNKNOWN (-3)
@@ -655,6 +658,120 @@ rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  uint64_t recovery_stride, uint64_t recovery_stripe_stride,
                                  const uint8_t *recovery_check, int32_t *d_located, uint8_t *d_mismatch, void *stream,
                                  rs_error *err);
+
+/* ---- robust locate: one corrupt original among corrupt recovery rows ----
+ * rs_locate_device needs every selected recovery row but the damage of the one
+ * original to be clean: it takes its candidate from the first two selected rows
+ * and gives up on the first row that disagrees, so one corrupt original plus one
+ * flipped bit in any recovery row comes back RS_LOCATE_UNKNOWN.  This call
+ * tolerates up to max_outliers corrupt selected rows beside the original, and
+ * names them.
+ *   Arguments: those of rs_locate_device[_batch], in the same order, with
+ * max_outliers after recovery_check and d_outlier after d_mismatch.  d_outlier:
+ * DEVICE array of stripes x recovery_count bytes, stripe-major and dense, like the
+ * flags.  With c = the number of selected rows and t = max_outliers the call
+ * requires 2 (1 + t) <= c and t <= RS_LOCATE_MAX_OUTLIERS.
+ *   Result: after the call every byte of d_mismatch, every word of d_located and
+ * every byte of d_outlier is defined.  d_mismatch is exactly what
+ * rs_verify_device_batch writes for the same arguments.  d_located[b] is
+ *   RS_LOCATE_CLEAN, RS_LOCATE_ROWS
+ *                      exactly as by rs_locate_device: fewer than c selected rows
+ *                      differ (with the same "NOT proven").  d_outlier of the
+ *                      stripe is all 0.
+ *   i in [0, original_count)
+ *                      every selected row differs, and there are one e per column
+ *                      and a set B of at most t selected rows such that D_j =
+ *                      G[j][i] * e in every column for every selected j outside B.
+ *                      d_outlier[b][j] = 1 exactly for j in B and 0 elsewhere,
+ *                      unselected rows included.  Handing original i and the rows
+ *                      of B to rs_repair_device* as absent heals the stripe.
+ *   RS_LOCATE_UNKNOWN  every selected row differs and no such (i, e, B) exists.
+ *                      d_outlier of the stripe is all 0.
+ * Nothing is written but the three outputs.
+ *   1. Uniqueness.  Two explanations (i, e, B) and (i', e', B') share at least
+ * c - 2t >= 2 selected rows outside B and B'.  If i != i', two such rows j, k give
+ * G[j][i] e = G[j][i'] e' and G[k][i] e = G[k][i'] e' in every column; the 2 x 2
+ * minor of G on rows j, k and columns i, i' does not vanish (the code is MDS), so
+ * e = e' = 0 in every column, and then D_j = 0: row j does not differ, against
+ * "every selected row differs".  If i = i', one shared row j gives G[j][i] e =
+ * G[j][i] e' with G[j][i] != 0, so e = e', and then B = B' = the selected rows
+ * with D_j != G[j][i] e.  So i, e and B are functions of the stripe's bytes, the
+ * mask and t alone, not of how they are found.
+ *   2. Trust.  Suppose the true damage is s corrupt shards, originals and selected
+ * recovery rows alike, with s + 1 + t <= c.  Then the call never names a wrong
+ * (i, B).  The originals and the c selected rows are a word of an
+ * [original_count + c, original_count] MDS code, of distance c + 1.  The stored
+ * word is within s of the true codeword; an answer (i, B) is a codeword (the
+ * originals with e taken off original i, and its encode) within 1 + |B| <= 1 + t
+ * of the stored word.  Were the two different, they would be two codewords within
+ * s + 1 + t <= c of one another, less than the distance.  So the answer's
+ * codeword IS the true one: i and B are among the truly corrupt shards.  This
+ * replaces rs_locate_device's "c - 1 corrupt shards" statement; at the largest
+ * allowed t = c/2 - 1 it is s <= c/2, the unique-decoding radius.
+ *   3. Compatibility.  With max_outliers == 0 the results in d_located and
+ * d_mismatch are those of rs_locate_device_batch for the same arguments (B is
+ * empty: the contract above is the locate's), and d_outlier is all zero.
+ *   Errors, all before any device work, in this order: rs_locate_device_batch's
+ * checks, with d_outlier among the null-pointer checks; then max_outliers >
+ * RS_LOCATE_MAX_OUTLIERS or 2 (1 + max_outliers) > c -> RS_ERR_INVALID_ARGUMENT;
+ * then the locate's shape bound.  stripes == 0: RS_OK, nothing launched or
+ * written, the context not touched.
+ *   How it is found.  Of the first t + 1 disjoint pairs of the selected-row list,
+ * (sel[0], sel[1]), (sel[2], sel[3]), ..., one at least has both rows outside B.
+ * Each pair p gives a candidate as rs_locate_device's two rows do: the first
+ * column where D_sel[2p] != 0, the log ratio against D_sel[2p+1] there, the i with
+ * that ratio in the table.  A candidate from a spoiled pair can be wrong, or right
+ * in i with a wrong e (its reference row an outlier damaged where e = 0).  So each
+ * candidate is confirmed with e from ITS OWN reference row, e = D_sel[2p] /
+ * G[sel[2p]][i_p], by counting the selected rows that disagree in any pack; the
+ * first candidate with at most t is the answer, and by 1. any that passes names
+ * the same (i, e, B).
+ *   Launches: the locate's up to k_verify_rows (its coefficient table shared with
+ * rs_locate_device and rs_heal_device both ways), d_outlier zeroed beside the
+ * flags; then per group of stripes a memset of (t + 1) x recovery_count vote bytes
+ * per stripe in per-stream scratch, k_locate_find_pairs (one workgroup per stripe
+ * and pair; CLEAN / ROWS from the flags, else the pair's candidate), k_locate_count (the
+ * confirm's grid; each row's D_j loaded once and checked against every
+ * candidate; a disagreeing lane stores the byte 1 to votes[stripe][p][j]) and
+ * k_locate_decide (one workgroup per stripe: the sums, d_located, the d_outlier
+ * row).
+ *   Measured (tools/locate_robust_time.py,
+ * profiles/locate_robust/locate_robust_time.txt; 1024:1024, every row, us per
+ * call, the legs interleaved in one session; locate = rs_locate_device_batch,
+ * whose kernels are the parent commit's -- the same legs on the parent's build
+ * read 22.27 / 240.35 / 126.12 clean and 25.83 / 266.20 / 163.87 corrupt; spread =
+ * max - min of its five rounds; original = one corrupt original in every stripe,
+ * outlier = the same plus one flipped bit in recovery row 0 of every stripe):
+ *     shape               locate clean (spread)  locate original (spread)  t=1 clean / original / outlier  t=7 clean / original / outlier
+ *     1 KiB, one stripe    23.64 (10.91)          26.19 (5.44)              29.93 /  34.92 /  34.13         32.32 /  40.06 /  39.74
+ *     1 KiB, 64 stripes   242.32 (0.88)          267.43 (0.57)             244.86 / 287.27 / 286.95        247.86 / 324.60 / 321.87
+ *     64 KiB, one stripe  123.97 (4.57)          164.07 (0.64)             129.35 / 187.97 / 186.83        130.17 / 215.34 / 213.09
+ * A clean batch costs the locate plus about one small launch, as expected: +6.3 /
+ * +2.5 / +5.4 us at t = 1, +8.7 / +5.6 / +6.2 at t = 7 (one kernel and two memsets
+ * more; the single 1 KiB stripe was bimodal in the session, 15 and 22-26 us).  The
+ * damaged case does NOT cost the locate's corrupt case: +8.7 / +19.8 / +23.9 us at
+ * t = 1 and +13.9 / +57.2 / +51.3 us at t = 7.  The find costs what the locate's
+ * does and the rows are read once; the excess is k_locate_count (39.8 / 47.5 us
+ * at t = 1, 78.4 / 73.4 at t = 7 by the events, against k_locate_confirm's 26.0 /
+ * 27.9): every workgroup of 16 rows first forms e for each of the t + 1
+ * candidates, and the candidate loop inside the row loop keeps loads and products
+ * of neighbouring rows from overlapping.  DESIGN.md "Robust locate" has the rest.
+ *   Not covered: writing the correction in place (a robust heal); two or more
+ * corrupt originals; a mask per stripe; stripes with missing originals; the host
+ * pipeline, the object API and the sharded classes. */
+#define RS_LOCATE_MAX_OUTLIERS 7u
+rs_status rs_locate_device_robust(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                  uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
+                                  const void *d_recovery, uint64_t recovery_stride, const uint8_t *recovery_check,
+                                  uint32_t max_outliers, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_outlier,
+                                  void *stream, rs_error *err);
+rs_status rs_locate_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                        uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                        const void *d_original, uint64_t original_stride,
+                                        uint64_t original_stripe_stride, const void *d_recovery,
+                                        uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                        const uint8_t *recovery_check, uint32_t max_outliers, int32_t *d_located,
+                                        uint8_t *d_mismatch, uint8_t *d_outlier, void *stream, rs_error *err);
 
 /* ---- heal: fix what the locate found, in place, on the device ----
  * A scrub built from the calls above is three calls with a host round trip in the

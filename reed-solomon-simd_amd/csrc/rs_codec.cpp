@@ -186,6 +186,7 @@ struct VerifyWs {
 struct LocateWs {
     DevBuf unit, coef, logs;
     DevBuf differ;  // rs_heal_device*: a group's counts of differing rows, one word per stripe
+    DevBuf robust;  // rs_locate_device_robust*: a group's candidates, then its vote bytes
     bool valid = false;  // `logs` holds the table of (high, n, m)
     int high = 0;
     uint64_t n = 0, m = 0;
@@ -2114,6 +2115,82 @@ void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
     }
 }
 
+// What rs_locate_device_robust* adds to a locate (DESIGN.md "Robust locate").
+struct RobustCall {
+    uint32_t max_outliers;
+    uint8_t *d_outlier;  // stripes x M
+};
+
+// locate_dev's sibling: the same group loop with k_locate_find_pairs, k_locate_count
+// and k_locate_decide where the locate has its find and confirm.  The caller has
+// checked 2 (1 + max_outliers) <= the selected rows, the shape bound and stripes > 0.
+// Per group the scratch holds (max_outliers + 1) candidates and vote rows per stripe.
+void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V,
+                       const RobustCall &R, hipStream_t s) {
+    const uint32_t M = uint32_t(V.M), t = R.max_outliers;
+    uint32_t lo = 0, hi = M, nsel = M;
+    if (V.mask) {
+        lo = M, hi = 0, nsel = 0;
+        for (uint32_t j = 0; j < M; ++j)
+            if (V.mask[j]) lo = std::min(lo, j), hi = j + 1, ++nsel;
+    }
+    const uint16_t *logs = locate_table(ctx, ws, high, V.N, V.M, s);
+    // every flag and every outlier byte is defined after the call: zero, then the kernels store the ones
+    check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
+    check(hipMemsetAsync(R.d_outlier, 0, V.stripes * V.M, s));
+    const uint8_t *d_sel = nullptr;
+    const uint32_t *d_list = nullptr;
+    if (nsel < M) verify_mask(ws, V.mask, M, nsel, s, &d_sel, &d_list);
+    const uint32_t n = uint32_t(next_pow2(high ? V.M : V.N)), L = ilog2(n);
+    const uint32_t C = uint32_t(((high ? V.N : V.M) + n - 1) / n);
+    const bool column = use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+    const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+
+    if (!ws.ver) ws.ver.reset(new VerifyWs);
+    const uint64_t W = g.stride, group = column ? kMaxBatchStripes : 1;
+    const uint64_t held = std::min<uint64_t>(group, V.stripes);  // stripes in scratch at a time
+    uint8_t *enc = static_cast<uint8_t *>(ws.ver->enc.get(held * V.M * W));
+    constexpr uint64_t kCands = rs::kRobustMaxOutliers + 1;
+    const uint64_t cand_bytes = held * kCands * 4, vote_bstride = uint64_t(t + 1) * V.M;
+    uint8_t *scratch = static_cast<uint8_t *>(ws.loc->robust.get(cand_bytes + held * vote_bstride));
+    Geom ge = g;
+    ge.rec_stride = W;
+    ge.orig_bstride = V.orig_bstride;
+    ge.rec_bstride = V.M * W;
+    for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
+        ge.stripes = uint32_t(std::min<uint64_t>(group, V.stripes - b0));
+        const uint8_t *o = V.d_orig + b0 * V.orig_bstride;
+        if (high) encode_high(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
+        else encode_low(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
+        rs::VerifyRowsArgs Q;
+        Q.want = enc, Q.want_stride = W, Q.want_bstride = V.M * W;
+        Q.have = V.d_rec + b0 * V.rec_bstride, Q.have_stride = g.rec(), Q.have_bstride = V.rec_bstride;
+        Q.rows = d_list, Q.nrows = nsel, Q.packs = g.packs, Q.stripes = ge.stripes;
+        Q.flags = V.d_flags + b0 * V.M, Q.flag_bstride = V.M;
+        Q.fmt = g.fmt;
+        update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(Q, s); });
+        rs::RobustArgs A;
+        A.want = Q.want, A.want_stride = W, A.want_bstride = Q.want_bstride;
+        A.have = Q.have, A.have_stride = Q.have_stride, A.have_bstride = Q.have_bstride;
+        A.rows = d_list, A.nsel = nsel, A.packs = g.packs, A.stripes = ge.stripes;
+        A.N = uint32_t(V.N), A.M = M;
+        A.flags = Q.flags, A.flag_bstride = V.M;
+        A.located = V.d_located + b0;
+        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
+        A.fmt = g.fmt;
+        A.t = t;
+        A.cand = reinterpret_cast<int32_t *>(scratch);
+        A.votes = scratch + cand_bytes, A.vote_bstride = vote_bstride;
+        A.outlier = R.d_outlier + b0 * V.M, A.outlier_bstride = V.M;
+        check(hipMemsetAsync(A.votes, 0, ge.stripes * vote_bstride, s));
+        // find: the flags, a word and the candidates per stripe.  count: as the compare,
+        // where it runs at all.  decide: the candidates, and a stripe that has one its votes
+        update_launch(s, (V.M + 4 + 4 * (t + 1)) * uint64_t(ge.stripes), [&] { return rs::launch_locate_find_pairs(A, s); });
+        update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_locate_count(A, s); });
+        update_launch(s, 4 * (t + 1) * uint64_t(ge.stripes), [&] { return rs::launch_locate_decide(A, s); });
+    }
+}
+
 const char *hip_msg(hipError_t e) { return hipGetErrorString(e); }
 
 }  // namespace
@@ -3159,6 +3236,58 @@ rs_status rs_locate_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M
                            rs_error *err) {
     return rs_locate_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
                                   d_located, d_mismatch, stream, err);
+}
+
+// ---- robust locate: one corrupt original among corrupt recovery rows (include/rs_mi355x.h) ----
+
+rs_status rs_locate_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                        uint64_t stripes, const void *d_orig, uint64_t orig_stride,
+                                        uint64_t orig_stripe_stride, const void *d_rec, uint64_t rec_stride,
+                                        uint64_t rec_stripe_stride, const uint8_t *recovery_check,
+                                        uint32_t max_outliers, int32_t *d_located, uint8_t *d_mismatch,
+                                        uint8_t *d_outlier, void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_located) || !ptr_ok(d_mismatch) || !ptr_ok(d_outlier))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    uint64_t nsel = M;
+    if (recovery_check) {
+        nsel = 0;
+        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
+    }
+    if (nsel < 2) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    // one clean pair among the first max_outliers + 1, and two clean rows shared by any two explanations
+    if (max_outliers > RS_LOCATE_MAX_OUTLIERS || 2 * (1 + uint64_t(max_outliers)) > nsel)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                      0, 0, recovery_check, d_mismatch},
+                     d_located};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        const RobustCall R{max_outliers, d_outlier};
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        locate_robust_dev(ctx, sw.w, high != 0, g, V, R, s);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_locate_device_robust(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const void *d_orig,
+                                  uint64_t orig_stride, const void *d_rec, uint64_t rec_stride,
+                                  const uint8_t *recovery_check, uint32_t max_outliers, int32_t *d_located,
+                                  uint8_t *d_mismatch, uint8_t *d_outlier, void *stream, rs_error *err) {
+    return rs_locate_device_robust_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0,
+                                         recovery_check, max_outliers, d_located, d_mismatch, d_outlier, stream, err);
 }
 
 // ---- heal: the locate that also writes the correction (include/rs_mi355x.h) ----

@@ -531,6 +531,30 @@ struct HealArgs : LocateArgs {
 };
 hipError_t launch_heal(const HealArgs &A, hipStream_t stream);
 
+// ---- robust locate (rs_locate_device_robust*, rs_locate_robust.hip; DESIGN.md "Robust locate") ----
+// After the unfused verify, as the locate's launches, with t <= kRobustMaxOutliers
+// and 2 (t + 1) <= nsel.  launch_locate_find_pairs (grid = stripes x pairs) writes every
+// located[b] -- kLocateClean / kLocateRows from the flags, else kLocateUnknown -- and
+// cand[b * (kRobustMaxOutliers + 1) + p] for p <= t: the original that pair p of the
+// selected-row list names, or -1.  launch_locate_count (the confirm's grid) stores
+// the byte 1 to votes[b * vote_bstride + p * M + j] where selected row j disagrees
+// with candidate p (e from the candidate's own reference row, sel[2p]); votes are
+// zeroed ahead of it.  launch_locate_decide (grid = stripes) stores the first
+// candidate with at most t bytes set to located[b] and those bytes to the zeroed
+// outlier[b * outlier_bstride + j].
+constexpr uint32_t kRobustMaxOutliers = 7;  // include/rs_mi355x.h RS_LOCATE_MAX_OUTLIERS
+struct RobustArgs : LocateArgs {
+    uint32_t t = 0;  // max_outliers
+    int32_t *cand = nullptr;
+    uint8_t *votes = nullptr;
+    uint64_t vote_bstride = 0;  // >= (t + 1) * M
+    uint8_t *outlier = nullptr;
+    uint64_t outlier_bstride = 0;
+};
+hipError_t launch_locate_find_pairs(const RobustArgs &A, hipStream_t stream);
+hipError_t launch_locate_count(const RobustArgs &A, hipStream_t stream);
+hipError_t launch_locate_decide(const RobustArgs &A, hipStream_t stream);
+
 // x[rows] *= exp(log_m) over `blocks` 64-byte blocks.
 hipError_t launch_mul(uint8_t *rows, uint64_t blocks, const uint32_t *lut_entry, hipStream_t stream);
 

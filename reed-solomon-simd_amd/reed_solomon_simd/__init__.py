@@ -123,6 +123,10 @@ _sig("rs_verify_set_fused", _int, _vp, _int)
 _sig("rs_locate_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, _vp, _vp, _vp, _E)
 _sig("rs_locate_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, _vp, _vp, _vp, _E)
+_sig("rs_locate_device_robust", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p,
+     ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
+_sig("rs_locate_device_robust_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     ctypes.c_char_p, ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_heal_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, ctypes.c_uint32,
      ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_heal_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
@@ -1223,6 +1227,91 @@ def locate_device_batch(original_count: int, recovery_count: int, shard_bytes: i
                                        d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows,
                                        _ptr(d_located), _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
     return d_located, d_mismatch
+
+
+LOCATE_MAX_OUTLIERS = 7  # RS_LOCATE_MAX_OUTLIERS (include/rs_mi355x.h)
+
+
+def _check_outlier(d_outlier, shape, like):
+    """The outlier tensor of a robust locate: the caller's (uint8, on the device, contiguous,
+    exactly `shape`) or a new one on the device of `like`."""
+    if d_outlier is None:
+        if not hasattr(like, "data_ptr"):
+            raise ValueError("d_outlier: needed when the matrices are raw pointers")
+        import torch
+        return torch.empty(shape, dtype=torch.uint8, device=like.device)
+    if hasattr(d_outlier, "data_ptr"):
+        if str(d_outlier.dtype) != "torch.uint8":
+            raise ValueError(f"d_outlier: dtype must be uint8, got {d_outlier.dtype}")
+        if not d_outlier.is_cuda:
+            raise ValueError("d_outlier: must be a device (cuda/HIP) tensor")
+        if tuple(d_outlier.shape) != tuple(shape) or not d_outlier.is_contiguous():
+            raise ValueError(f"d_outlier: expected a contiguous tensor of shape {tuple(shape)}, "
+                             f"got {tuple(d_outlier.shape)}")
+    return d_outlier
+
+
+def _robust_args(recovery_rows, recovery_count, max_outliers):
+    rows = _locate_mask(recovery_rows, recovery_count)
+    t, c = int(max_outliers), recovery_count if rows is None else sum(1 for b in rows if b)
+    if not 0 <= t <= LOCATE_MAX_OUTLIERS:
+        raise ValueError(f"max_outliers: 0 .. {LOCATE_MAX_OUTLIERS}, got {max_outliers}")
+    if 2 * (1 + t) > c:
+        raise ValueError(f"max_outliers: {t} outliers need {2 * (1 + t)} selected recovery rows at least, got {c}")
+    return rows, t
+
+
+def locate_device_robust(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                         recovery_rows=None, max_outliers: int = 1, d_located=None, d_mismatch=None, d_outlier=None,
+                         stream=None, rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """locate_device that tolerates up to max_outliers corrupt selected recovery rows beside the
+    one corrupt original, and names them (rs_locate_device_robust).  Returns (located, mismatch,
+    outlier): locate_device's two, and a uint8 tensor [recovery_count] holding 1 for each selected
+    row that disagrees with the located original's error (all 0 unless located >= 0).  Handing
+    original `located` and those rows to repair_device* as absent heals the stripe.  Needs
+    2 * (1 + max_outliers) selected rows; max_outliers <= LOCATE_MAX_OUTLIERS.  Asynchronous on
+    `stream`."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows, t = _robust_args(recovery_rows, recovery_count, max_outliers)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    d_located = _check_located(d_located, (1,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    d_outlier = _check_outlier(d_outlier, (recovery_count,), d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_locate_device_robust(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
+                                        _ptr(d_original), _row_stride(d_original), _ptr(d_recovery),
+                                        _row_stride(d_recovery), rows, t, _ptr(d_located), _ptr(d_mismatch),
+                                        _ptr(d_outlier), _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_outlier
+
+
+def locate_device_robust_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                               recovery_rows=None, max_outliers: int = 1, d_located=None, d_mismatch=None,
+                               d_outlier=None, stream=None, rate_: int = RATE_DEFAULT,
+                               ctx: Optional[Context] = None):
+    """locate_device_robust on a batch of stripes sharing ONE row mask and one max_outliers
+    (rs_locate_device_robust_batch); tensors [stripes, rows, shard_bytes].  Returns (located
+    [stripes], mismatch [stripes, recovery_count], outlier [stripes, recovery_count])."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows, t = _robust_args(recovery_rows, recovery_count, max_outliers)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_outlier = _check_outlier(d_outlier, (n, recovery_count), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_locate_device_robust_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                              d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b,
+                                              rows, t, _ptr(d_located), _ptr(d_mismatch), _ptr(d_outlier),
+                                              _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_outlier
 
 
 HEAL_ORIGINAL = 1  # RS_HEAL_ORIGINAL (include/rs_mi355x.h)
