@@ -756,9 +756,10 @@ rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
  * 27.9): every workgroup of 16 rows first forms e for each of the t + 1
  * candidates, and the candidate loop inside the row loop keeps loads and products
  * of neighbouring rows from overlapping.  DESIGN.md "Robust locate" has the rest.
- *   Not covered: writing the correction in place (a robust heal); two or more
- * corrupt originals; a mask per stripe; stripes with missing originals; the host
- * pipeline, the object API and the sharded classes. */
+ *   rs_heal_device_robust below is this call
+ * writing the correction in place (a robust heal).
+ *   Not covered: two or more corrupt originals; a mask per stripe; stripes with
+ * missing originals; the host pipeline, the object API and the sharded classes. */
 #define RS_LOCATE_MAX_OUTLIERS 7u
 rs_status rs_locate_device_robust(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
                                   uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
@@ -871,6 +872,136 @@ rs_status rs_heal_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_
                                uint64_t recovery_stripe_stride, const uint8_t *recovery_check, uint32_t mode,
                                uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action,
                                void *stream, rs_error *err);
+
+/* ---- robust heal: heal the original and its outlier rows, in place ----
+ * rs_heal_device is built on the plain locate, so one rotten original plus a
+ * flipped bit in some recovery row comes back RS_LOCATE_UNKNOWN with action 0, and
+ * the caller is back to the three-call scrub: rs_locate_device_robust_batch, a
+ * synchronize and a host read of three arrays, rs_repair_device_batch_masks.  Yet
+ * after the robust locate everything a heal needs is on the device: d_located[b] =
+ * i, the set B in d_outlier, the encode of the stored originals (want) in
+ * per-stream scratch and the table log G.  The error is e = D_r / G[r][i] per
+ * column for any selected row r outside B (each gives the same e, by the robust
+ * locate's contract); the clean original is original_i ^ e; and the clean value of
+ * a row j of B is want_j ^ G[j][i] * e, by the encode's linearity (the identity
+ * rs_update_device rests on): encode(originals with e taken off original i)_j =
+ * encode(stored originals)_j ^ G[j][i] * e.  This call is the robust locate
+ * followed by one more launch per group of stripes that writes those: no decode,
+ * no second encode, no host round trip.
+ *   Arguments: those of rs_heal_device[_batch], in the same order, with
+ * max_outliers before mode and d_outlier between d_mismatch and d_action.
+ * Strides (0 = dense), alignment rules, the byte-wise path, the block and tail
+ * layout and the HOST mask recovery_check (NULL = every row; ONE mask for every
+ * stripe) are unchanged; rows marked 0 are never read and never written.
+ * Asynchronous on `stream`; scratch per (context, stream).  With c = the number of
+ * selected rows and t = max_outliers: 2 (1 + t) <= c, t <= RS_LOCATE_MAX_OUTLIERS.
+ *   Result.  d_located, d_mismatch and d_outlier hold exactly what
+ * rs_locate_device_robust_batch writes for the same arguments: they describe the
+ * stripe AS FOUND.  Every byte of d_action is defined; it is a bit set, and unlike
+ * rs_heal_device's it can be RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY:
+ *   d_located[b] = i >= 0, outlier set B
+ *     RS_HEAL_ORIGINAL in mode: original i of stripe b has become original_i ^ e,
+ *                     e = D_r / G[r][i] per column, r the first selected row
+ *                     outside B.  Only its shard_bytes bytes are written, not the
+ *                     row padding.  The action has the bit.
+ *     RS_HEAL_RECOVERY in mode, B not empty: every row j of B of d_recovery has
+ *                     become want_j ^ G[j][i] * e (a zero coefficient contributes
+ *                     nothing), shard_bytes bytes per row.  The action has the
+ *                     bit; with B empty it has not.  max_rows does not apply:
+ *                     |B| <= max_outliers already.
+ *     With both bits every selected row agrees afterwards; and if the true damage
+ *     is s corrupt shards with s + 1 + t <= c (the robust locate's fact 2), both
+ *     matrices are byte-identical to the clean stripe.  With one bit only the
+ *     other half is left as found, and the next scan reports it: after
+ *     RS_HEAL_ORIGINAL alone, RS_LOCATE_ROWS with exactly the rows of B flagged
+ *     (which RS_HEAL_RECOVERY then rewrites, max_rows permitting); after
+ *     RS_HEAL_RECOVERY alone, original i again, with no outliers -- by the plain
+ *     locate as well.
+ *   d_located[b] = RS_LOCATE_ROWS
+ *                     exactly as rs_heal_device: RS_HEAL_RECOVERY in mode and at
+ *                     most max_rows selected rows differ: each differing selected
+ *                     row has become the encode of the stored originals, and the
+ *                     action is RS_HEAL_RECOVERY.
+ *   anything else     action 0, the stripe untouched.
+ * Nothing else is written anywhere.  A second call on a stripe healed with both
+ * bits reports RS_LOCATE_CLEAN, action 0, an all-zero d_outlier, and writes
+ * nothing else.  With max_outliers == 0 the four outputs and both matrices equal
+ * rs_heal_device_batch's for the same arguments, and d_outlier is all zero.
+ *   CAVEATS.  The heal's "NOT proven", carried over: a ROWS stripe does not prove
+ * the originals intact, and RS_HEAL_RECOVERY can make recovery rows consistent
+ * with CORRUPT originals; keep max_rows well below half of the selected rows.  And
+ * the robust locate's trust bound: beyond s + 1 + t <= c the located answer is a
+ * codeword within 1 + t of the stored word, not necessarily the true one, and this
+ * call writes it.  Keep t small against c.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * d_recovery, d_located, d_mismatch, d_outlier or d_action ->
+ * RS_ERR_INVALID_ARGUMENT; rs_validate; the two row strides; mode == 0 or a bit
+ * outside the two; fewer than 2 selected rows, or fewer than 3 with
+ * RS_HEAL_ORIGINAL; max_outliers > RS_LOCATE_MAX_OUTLIERS or 2 (1 + max_outliers)
+ * > c; the locate's shape bound -- each RS_ERR_INVALID_ARGUMENT.  At max_outliers
+ * = 0 this is rs_heal_device_batch's order.  stripes == 0: RS_OK, nothing launched
+ * or written, the context not touched.  The matrices must not overlap one another
+ * or the four outputs.
+ *   Launches: the robust locate's, its coefficient table shared with the locate,
+ * the heal and the robust locate both ways; and one k_heal_robust per group of
+ * stripes directly after that group's k_locate_decide, while the group's encode is
+ * still in scratch (off the column kernel a group is one stripe and the scratch is
+ * reused).  k_heal_robust has the confirm's grid; workgroups of a stripe with
+ * nothing to do, and row groups with no row to write, leave at once.  On a located
+ * stripe a workgroup finds r by a scan of at most t + 1 outlier bytes, forms e
+ * once, row group 0 writes the original and every row group its rows of B; a ROWS
+ * stripe's count of differing rows is summed from its flags by the workgroup.  No
+ * ordering hazard by construction: e comes from row r and from scratch, neither
+ * ever written; each pack of original i is read-modify-written by one lane; each
+ * outlier row is written by the one workgroup that owns it, which reads only
+ * scratch.
+ *   Measured (tools/heal_robust_time.py,
+ * profiles/heal_robust/heal_robust_time.txt; 1024:1024, every row, both mode bits,
+ * max_rows 16, us per call, the legs interleaved in one session; locate =
+ * rs_locate_device_robust_batch on the same inputs, whose kernels are the parent
+ * commit's -- its legs on the parent's build in the same session read 33.83 /
+ * 246.08 / 129.02 clean at t = 1 and 34.79 / 246.91 / 129.20 at t = 7
+ * (heal_robust_time_parent.txt); spread = max - min of its five rounds; outlier =
+ * one corrupt original plus a flipped bit in recovery row 0 of EVERY stripe, row =
+ * one corrupt recovery row in every stripe; scrub = the three calls with their
+ * synchronize, host read and masks for the outlier damage; the damaged heal and
+ * scrub legs net of the 4.3-6.4 us launch that puts the damage back):
+ *     shape, t              locate clean (spread) / outlier / row   heal clean / outlier / row    scrub outlier
+ *     1 KiB, one stripe, 1   27.33 (2.90) /  33.14 /  31.99          35.10 /  35.56 /  36.32       140.84
+ *     1 KiB, one stripe, 7   26.55 (0.28) /  39.18 /  32.81          35.26 /  41.81 /  36.45       146.52
+ *     1 KiB, 64 stripes, 1  247.23 (1.32) / 289.74 / 247.60         249.07 / 302.53 / 253.65      1074.69
+ *     1 KiB, 64 stripes, 7  247.46 (0.68) / 324.88 / 247.95         249.06 / 338.11 / 254.00      1108.66
+ *     64 KiB, one stripe, 1 132.55 (1.21) / 189.86 / 130.44         134.02 / 196.38 / 136.07       494.20
+ *     64 KiB, one stripe, 7 132.94 (0.85) / 216.84 / 131.51         134.78 / 223.41 / 136.98       522.24
+ * A clean heal costs the robust locate plus one small launch, k_heal_robust at the
+ * 6.1-6.2 us floor by the events: +1.8 / +1.6 us on 64 stripes and +1.5 / +1.8 us
+ * at 64 KiB, inside the yardstick's spread plus one floor as expected.  The single
+ * 1 KiB stripe reads +7.8 us at t = 1 (spread 2.9: inside) and +8.7 us at t = 7
+ * (spread 0.3: 2 us OUTSIDE the expectation); that shape is launch-bound and
+ * moved by as much between two processes of the same kernels (the parent's
+ * build read 33.8 / 34.8 us for the 27.3 / 26.6 us leg).  A damaged heal costs the
+ * robust locate's damaged case plus that launch: +2.4 / +12.8 / +6.5 us at t = 1
+ * and +2.6 / +13.2 / +6.6 us at t = 7 for the outlier case (k_heal_robust 8.8 /
+ * 16.0 / 10.2 us by the events: one original and one row read and written per
+ * stripe), +3.7-4.3 / +6.1 / +5.5 us for a row.  It beats the three-call scrub by
+ * 105 / 772 / 298 us (4.0 / 3.6 / 2.5 times at t = 1, 3.5 / 3.3 / 2.3 at t = 7),
+ * more than the scrub's decode (k_mono_repair_masks 20 / 614 us, the 64 KiB
+ * decode's launches 212 us by the events), the rest being the synchronize, the
+ * three reads on the host and the masks.  DESIGN.md "Robust heal" has the rest.
+ *   Not covered: two or more corrupt originals; a mask per stripe; stripes with
+ * missing originals; the host pipeline, the object API and the sharded classes. */
+rs_status rs_heal_device_robust(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                uint64_t shard_bytes, void *d_original, uint64_t original_stride, void *d_recovery,
+                                uint64_t recovery_stride, const uint8_t *recovery_check, uint32_t max_outliers,
+                                uint32_t mode, uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch,
+                                uint8_t *d_outlier, uint8_t *d_action, void *stream, rs_error *err);
+rs_status rs_heal_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                      uint64_t shard_bytes, uint64_t stripes, void *d_original,
+                                      uint64_t original_stride, uint64_t original_stripe_stride, void *d_recovery,
+                                      uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                      const uint8_t *recovery_check, uint32_t max_outliers, uint32_t mode,
+                                      uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_outlier,
+                                      uint8_t *d_action, void *stream, rs_error *err);
 
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x

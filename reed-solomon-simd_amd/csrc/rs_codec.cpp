@@ -2125,8 +2125,10 @@ struct RobustCall {
 // and k_locate_decide where the locate has its find and confirm.  The caller has
 // checked 2 (1 + max_outliers) <= the selected rows, the shape bound and stripes > 0.
 // Per group the scratch holds (max_outliers + 1) candidates and vote rows per stripe.
+// With a heal (rs_heal_device_robust*), k_heal_robust is a fourth launch, inside the
+// loop as k_heal is in locate_dev's: it reads the group's encode and d_outlier rows.
 void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V,
-                       const RobustCall &R, hipStream_t s) {
+                       const RobustCall &R, hipStream_t s, const HealCall *H = nullptr) {
     const uint32_t M = uint32_t(V.M), t = R.max_outliers;
     uint32_t lo = 0, hi = M, nsel = M;
     if (V.mask) {
@@ -2169,7 +2171,7 @@ void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g,
         Q.flags = V.d_flags + b0 * V.M, Q.flag_bstride = V.M;
         Q.fmt = g.fmt;
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(Q, s); });
-        rs::RobustArgs A;
+        rs::HealRobustArgs A;  // the robust locate's kernels take its RobustArgs
         A.want = Q.want, A.want_stride = W, A.want_bstride = Q.want_bstride;
         A.have = Q.have, A.have_stride = Q.have_stride, A.have_bstride = Q.have_bstride;
         A.rows = d_list, A.nsel = nsel, A.packs = g.packs, A.stripes = ge.stripes;
@@ -2188,6 +2190,14 @@ void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g,
         update_launch(s, (V.M + 4 + 4 * (t + 1)) * uint64_t(ge.stripes), [&] { return rs::launch_locate_find_pairs(A, s); });
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_locate_count(A, s); });
         update_launch(s, 4 * (t + 1) * uint64_t(ge.stripes), [&] { return rs::launch_locate_decide(A, s); });
+        if (!H) continue;
+        A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
+        A.rec = H->d_rec + b0 * V.rec_bstride;
+        A.mode = H->mode, A.max_rows = H->max_rows;
+        A.action = H->d_action + b0;
+        // a stripe with nothing to heal costs a word; a located one three rows and two per
+        // outlier row, a ROWS one two per rewritten row
+        update_launch(s, 5 * uint64_t(ge.stripes), [&] { return rs::launch_heal_robust(A, s); });
     }
 }
 
@@ -3339,6 +3349,64 @@ rs_status rs_heal_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, 
                          void *stream, rs_error *err) {
     return rs_heal_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
                                 mode, max_rows, d_located, d_mismatch, d_action, stream, err);
+}
+
+// ---- robust heal: the robust locate that also writes the correction (include/rs_mi355x.h) ----
+
+rs_status rs_heal_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                      uint64_t stripes, void *d_orig, uint64_t orig_stride,
+                                      uint64_t orig_stripe_stride, void *d_rec, uint64_t rec_stride,
+                                      uint64_t rec_stripe_stride, const uint8_t *recovery_check,
+                                      uint32_t max_outliers, uint32_t mode, uint32_t max_rows, int32_t *d_located,
+                                      uint8_t *d_mismatch, uint8_t *d_outlier, uint8_t *d_action, void *stream,
+                                      rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_located) || !ptr_ok(d_mismatch) ||
+        !ptr_ok(d_outlier) || !ptr_ok(d_action))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    uint64_t nsel = M;
+    if (recovery_check) {
+        nsel = 0;
+        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
+    }
+    // the heal's rows (three to write an original on the evidence), then the robust locate's
+    if (nsel < ((mode & RS_HEAL_ORIGINAL) ? 3u : 2u)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (max_outliers > RS_LOCATE_MAX_OUTLIERS || 2 * (1 + uint64_t(max_outliers)) > nsel)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                      0, 0, recovery_check, d_mismatch},
+                     d_located};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        const RobustCall R{max_outliers, d_outlier};
+        const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        locate_robust_dev(ctx, sw.w, high != 0, g, V, R, s, &H);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_heal_device_robust(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, void *d_orig,
+                                uint64_t orig_stride, void *d_rec, uint64_t rec_stride, const uint8_t *recovery_check,
+                                uint32_t max_outliers, uint32_t mode, uint32_t max_rows, int32_t *d_located,
+                                uint8_t *d_mismatch, uint8_t *d_outlier, uint8_t *d_action, void *stream,
+                                rs_error *err) {
+    return rs_heal_device_robust_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0,
+                                       recovery_check, max_outliers, mode, max_rows, d_located, d_mismatch, d_outlier,
+                                       d_action, stream, err);
 }
 
 // ---- encoder ----------------------------------------------------------------

@@ -555,6 +555,23 @@ hipError_t launch_locate_find_pairs(const RobustArgs &A, hipStream_t stream);
 hipError_t launch_locate_count(const RobustArgs &A, hipStream_t stream);
 hipError_t launch_locate_decide(const RobustArgs &A, hipStream_t stream);
 
+// ---- robust heal (rs_heal_device_robust*, rs_locate_robust.hip; DESIGN.md "Robust heal") ----
+// After launch_locate_decide of the same RobustArgs, while the encode is still in
+// `want`.  launch_heal_robust (the confirm's grid) writes every action[b], a bit set,
+// and the stripe: located[b] = i >= 0: with e = D_r / G[r][i] (r: the first selected
+// row with outlier[b][r] = 0), kHealOriginal (the mode bit): original i ^= e over every
+// pack; kHealRecovery (the mode bit, some outlier byte set): every row j of `rec` with
+// outlier[b][j] set = row j of `want` ^ G[j][i] * e.  located[b] = kLocateRows: as
+// launch_heal, the count of differing rows summed from the flags.  rec is the matrix
+// `have` names.
+struct HealRobustArgs : RobustArgs {
+    uint8_t *orig = nullptr, *rec = nullptr;
+    uint64_t orig_stride = 0, orig_bstride = 0;
+    uint32_t mode = 0, max_rows = 0;
+    uint8_t *action = nullptr;  // one byte per stripe
+};
+hipError_t launch_heal_robust(const HealRobustArgs &A, hipStream_t stream);
+
 // x[rows] *= exp(log_m) over `blocks` 64-byte blocks.
 hipError_t launch_mul(uint8_t *rows, uint64_t blocks, const uint32_t *lut_entry, hipStream_t stream);
 

@@ -21,6 +21,26 @@
 //                        bytes set gives located[b] and its bytes the stripe's
 //                        outlier row; none: RS_LOCATE_UNKNOWN
 //
+//
+// A robust heal (rs_heal_device_robust*, DESIGN.md "Robust heal") adds one launch
+// after k_locate_decide, while the encode is still in scratch:
+//
+//   k_heal_robust        the confirm's grid.  A located stripe (i, B): e = D_r / G[r][i]
+//                        from the first selected row r outside B; row group 0 writes
+//                        original_i ^= e, and every row group writes its rows j of B as
+//                        want_j ^ G[j][i] * e (the encode's linearity: that is the
+//                        encode of the originals with e taken off original i).  A ROWS
+//                        stripe: k_heal's copy of the flagged rows from the encode,
+//                        when at most max_rows differ
+//
+// No ordering hazard inside k_heal_robust, by construction: e comes from row r of the
+// caller's recovery matrix and from scratch, and neither is ever written (r is outside
+// B, and only rows of B are stored to on a located stripe); each pack of original i is
+// read-modify-written by exactly one lane (row group 0 of its pack tile); each outlier
+// row is written by the one workgroup per pack tile that owns it, from scratch and e
+// alone; a ROWS stripe's rows are copied from scratch.  The caller's matrices must not
+// overlap one another or the four outputs.
+//
 // ConstWords, ld_syndrome and coef_log are rs_locate.hip's (copied: that file's
 // kernels are not to move).
 #include <cstdio>
@@ -234,6 +254,111 @@ __global__ __launch_bounds__(kFindThreads) void k_locate_decide(const RobustArgs
     // CLEAN, ROWS or UNKNOWN, as k_locate_find_pairs left it
 }
 
+// The confirm's grid, after k_locate_decide.  Every branch but the pack bound is uniform
+// over the workgroup; workgroup (0, 0) of a stripe stores action[b]; a stripe with
+// nothing to heal (the common one of a scrub) leaves at once, and so does a row
+// group with no row to write.
+__global__ __launch_bounds__(256) void k_heal_robust(const HealRobustArgs A) {
+    __shared__ uint32_t s_count;
+    const uint64_t b = blockIdx.z;
+    const uint32_t tid = threadIdx.x;
+    const int32_t loc = __builtin_amdgcn_readfirstlane(A.located[b]);
+    const bool first = (blockIdx.x | blockIdx.y) == 0;
+    const bool rec_bit = (A.mode & kHealRecovery) != 0;
+    if (loc < 0 && !(loc == kLocateRows && rec_bit)) {  // CLEAN, UNKNOWN, or ROWS with its bit off
+        if (first && tid == 0) A.action[b] = 0;
+        return;
+    }
+    const ConstWords rows = const_words(A.rows);
+    // what names the rows to write: the outlier bytes of a located stripe, the flags of a ROWS one
+    const uint8_t *marks = loc >= 0 ? A.outlier + b * A.outlier_bstride : A.flags + b * A.flag_bstride;
+    const uint32_t r0 = blockIdx.y * A.rows_per_group;  // (rows_per_group <= 16)
+    const uint32_t r1 = r0 + A.rows_per_group < A.nsel ? r0 + A.rows_per_group : A.nsel;
+    uint32_t mine = 0;  // bit r - r0: this group's selected row r is marked
+    if (rec_bit)
+        for (uint32_t r = r0; r < r1; ++r) {
+            const uint32_t j = A.rows ? rows[r] : r;
+            mine |= uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(marks[j])) != 0) << (r - r0);
+        }
+    const uint32_t pk = blockIdx.x * blockDim.x + tid;
+    const bool ok = pk < A.packs;
+    const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
+    const uint8_t *want = A.want + b * A.want_bstride;
+    uint8_t *rec = A.rec + b * A.have_bstride;
+
+    if (loc >= 0) {
+        const bool write_orig = (A.mode & kHealOriginal) && blockIdx.y == 0;
+        if (first) {
+            uint32_t action = A.mode & kHealOriginal;
+            if (rec_bit) {  // B is not empty?  (unselected rows' bytes are zero)
+                uint32_t c = 0;
+                for (uint32_t j = tid; j < A.M; j += blockDim.x) c |= marks[j];
+                if (__syncthreads_or(int(c))) action |= kHealRecovery;
+            }
+            if (tid == 0) A.action[b] = uint8_t(action);
+        }
+        if (!write_orig && !mine) return;
+        // r: one of the first t + 1 selected rows is outside B
+        uint32_t ref = 0;
+        for (uint32_t q = 0; q <= A.t; ++q) {
+            ref = A.rows ? rows[q] : q;
+            if (!__builtin_amdgcn_readfirstlane(uint32_t(marks[ref]))) break;
+        }
+        // e = D_r / G[r][i], once per workgroup (the log is not the sentinel: row r differs and agrees)
+        const ConstWords logs = const_words(A.logs), lut = const_words(A.lut);
+        const uint32_t inv = (65535u - coef_log(logs, A.N, ref, uint32_t(loc))) % 65535u;
+        uint32_t t[kTableWords], l0 = 0, h0 = 0, el = 0, eh = 0;
+#pragma unroll
+        for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(inv) * kTableWords + w];
+        if (ok) ld_syndrome(A, want, A.have + b * A.have_bstride, ref, io, l0, h0);
+        gf_muladd4(el, eh, l0, h0, t);
+        if (write_orig && ok) {
+            uint8_t *p = A.orig + b * A.orig_bstride + uint64_t(loc) * A.orig_stride + io.lo;
+            st_word(p, ld_word(p, io) ^ el, io);
+            st_word(p + io.hi_delta, ld_word(p + io.hi_delta, io) ^ eh, io);
+        }
+        for (uint32_t r = r0; mine >> (r - r0); ++r) {
+            if (!((mine >> (r - r0)) & 1u)) continue;
+            const uint32_t j = A.rows ? rows[r] : r;
+            // want_j ^ G[j][i] * e; a zero coefficient (the sentinel) contributes nothing
+            const uint32_t lg = coef_log(logs, A.N, j, uint32_t(loc));
+            uint32_t pl = 0, ph = 0;
+            if (lg != kNoLog) {
+#pragma unroll
+                for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(lg) * kTableWords + w];
+                gf_muladd4(pl, ph, el, eh, t);
+            }
+            if (!ok) continue;
+            const uint8_t *w = want + uint64_t(j) * A.want_stride + io.lo;
+            uint8_t *h = rec + uint64_t(j) * A.have_stride + io.lo;
+            st_word(h, ld_word(w, io) ^ pl, io);
+            st_word(h + io.hi_delta, ld_word(w + io.hi_delta, io) ^ ph, io);
+        }
+        return;
+    }
+
+    // a ROWS stripe with its bit on: k_heal's copy, the count of differing selected rows
+    // summed here (unselected rows' flags are zero)
+    if (!first && !mine) return;
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    uint32_t c = 0;
+    for (uint32_t j = tid; j < A.M; j += blockDim.x) c += marks[j] != 0;
+    if (c) atomicAdd(&s_count, c);
+    __syncthreads();
+    const bool heal = s_count <= A.max_rows;
+    if (first && tid == 0) A.action[b] = uint8_t(heal ? kHealRecovery : 0u);
+    if (!heal || !ok) return;
+    for (uint32_t r = r0; mine >> (r - r0); ++r) {
+        if (!((mine >> (r - r0)) & 1u)) continue;
+        const uint32_t j = A.rows ? rows[r] : r;
+        const uint8_t *w = want + uint64_t(j) * A.want_stride + io.lo;
+        uint8_t *h = rec + uint64_t(j) * A.have_stride + io.lo;
+        st_word(h, ld_word(w, io), io);
+        st_word(h + io.hi_delta, ld_word(w + io.hi_delta, io), io);
+    }
+}
+
 // The confirm's grid (launch_locate_confirm).
 bool count_grid(RobustArgs &A, dim3 &grid, uint32_t &threads) {
     threads = A.packs >= 256 ? 256u : (A.packs + 63u) / 64u * 64u;
@@ -277,6 +402,20 @@ hipError_t launch_locate_decide(const RobustArgs &A, hipStream_t s) {
     if (!robust_ok(A)) return hipErrorInvalidValue;
     k_locate_decide<<<dim3(A.stripes), kFindThreads, 0, s>>>(A);
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_decide");
+    return hipGetLastError();
+}
+
+hipError_t launch_heal_robust(const HealRobustArgs &A0, hipStream_t s) {
+    if (!A0.stripes) return hipSuccess;
+    if (!robust_ok(A0) || A0.stripes > 65535 || !A0.flags || !A0.located || !A0.action || !A0.orig || !A0.rec ||
+        !A0.mode || (A0.mode & ~(kHealOriginal | kHealRecovery)))
+        return hipErrorInvalidValue;
+    HealRobustArgs A = A0;
+    dim3 grid;
+    uint32_t threads;
+    if (!count_grid(A, grid, threads)) return hipErrorInvalidValue;
+    k_heal_robust<<<grid, threads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_heal_robust");
     return hipGetLastError();
 }
 

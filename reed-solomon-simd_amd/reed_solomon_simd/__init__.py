@@ -131,6 +131,10 @@ _sig("rs_heal_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, 
      ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_heal_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
+_sig("rs_heal_device_robust", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p,
+     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _E)
+_sig("rs_heal_device_robust_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _E)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -1401,6 +1405,71 @@ def heal_device_batch(original_count: int, recovery_count: int, shard_bytes: int
                                      max_rows, _ptr(d_located), _ptr(d_mismatch), _ptr(d_action), _stream(stream),
                                      ctypes.byref(err)), err)
     return d_located, d_mismatch, d_action
+
+
+def _heal_robust_args(recovery_rows, recovery_count, max_outliers, mode, max_rows):
+    """The heal's checks, then the robust locate's (the library's order)."""
+    rows, mode, max_rows = _heal_args(recovery_rows, recovery_count, mode, max_rows)
+    return rows, _robust_args(recovery_rows, recovery_count, max_outliers)[1], mode, max_rows
+
+
+def heal_device_robust(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                       recovery_rows=None, max_outliers: int = 1, mode: int = HEAL_ORIGINAL | HEAL_RECOVERY,
+                       max_rows: int = 0, d_located=None, d_mismatch=None, d_outlier=None, d_action=None, stream=None,
+                       rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """locate_device_robust that also writes the correction, in place (rs_heal_device_robust).
+    For a located original i with outlier rows B: mode & HEAL_ORIGINAL makes original i
+    original_i ^ e, mode & HEAL_RECOVERY makes every row j of B the encode of the stored
+    originals ^ G[j][i] * e -- with both bits the stripe is consistent afterwards, and clean
+    within the robust locate's trust bound.  A LOCATE_ROWS stripe is treated as by heal_device
+    (HEAL_RECOVERY, at most max_rows differing rows; the same caveat).  Returns (located, mismatch,
+    outlier, action): the robust locate's report of the stripe as found, and a uint8 tensor [1]
+    holding the bits of what was written (0: untouched).  Asynchronous on `stream`."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows, t, mode, max_rows = _heal_robust_args(recovery_rows, recovery_count, max_outliers, mode, max_rows)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    d_located = _check_located(d_located, (1,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    d_outlier = _check_outlier(d_outlier, (recovery_count,), d_recovery)
+    d_action = _check_action(d_action, (1,), d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_heal_device_robust(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
+                                      _ptr(d_original), _row_stride(d_original), _ptr(d_recovery),
+                                      _row_stride(d_recovery), rows, t, mode, max_rows, _ptr(d_located),
+                                      _ptr(d_mismatch), _ptr(d_outlier), _ptr(d_action), _stream(stream),
+                                      ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_outlier, d_action
+
+
+def heal_device_robust_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                             recovery_rows=None, max_outliers: int = 1, mode: int = HEAL_ORIGINAL | HEAL_RECOVERY,
+                             max_rows: int = 0, d_located=None, d_mismatch=None, d_outlier=None, d_action=None,
+                             stream=None, rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """heal_device_robust on a batch of stripes sharing ONE row mask and one max_outliers
+    (rs_heal_device_robust_batch); tensors [stripes, rows, shard_bytes].  Returns (located
+    [stripes], mismatch [stripes, recovery_count], outlier [stripes, recovery_count], action
+    [stripes])."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    rows, t, mode, max_rows = _heal_robust_args(recovery_rows, recovery_count, max_outliers, mode, max_rows)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_outlier = _check_outlier(d_outlier, (n, recovery_count), d_recovery)
+    d_action = _check_action(d_action, (n,), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_heal_device_robust_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                            d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b,
+                                            rows, t, mode, max_rows, _ptr(d_located), _ptr(d_mismatch),
+                                            _ptr(d_outlier), _ptr(d_action), _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_outlier, d_action
 
 
 class DeviceCall:
