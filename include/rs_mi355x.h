@@ -639,7 +639,8 @@ rs_status rs_verify_set_fused(rs_context *ctx, int mode);
  * cheaper first pass of a scrub that expects no corrupt originals.  DESIGN.md
  * "Locate" has the rest.
  *   Not covered: a mask per stripe; stripes with missing
- * originals; the host pipeline, the object API and the sharded classes; a fused
+ * originals (rs_locate_device_degraded below locates in those); the host
+ * pipeline, the object API and the sharded classes; a fused
  * form on k_mono_verify.  (One corrupt original together with corrupt recovery
  * rows: rs_locate_device_robust below.  Writing the correction back:
  * rs_heal_device below.) */
@@ -759,7 +760,8 @@ rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
  *   rs_heal_device_robust below is this call
  * writing the correction in place (a robust heal).
  *   Not covered: two or more corrupt originals; a mask per stripe; stripes with
- * missing originals; the host pipeline, the object API and the sharded classes. */
+ * missing originals (rs_locate_device_degraded below locates in those); the host
+ * pipeline, the object API and the sharded classes. */
 #define RS_LOCATE_MAX_OUTLIERS 7u
 rs_status rs_locate_device_robust(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
                                   uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
@@ -773,6 +775,147 @@ rs_status rs_locate_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t 
                                         uint64_t recovery_stride, uint64_t recovery_stripe_stride,
                                         const uint8_t *recovery_check, uint32_t max_outliers, int32_t *d_located,
                                         uint8_t *d_mismatch, uint8_t *d_outlier, void *stream, rs_error *err);
+
+/* ---- degraded locate: the locate of a stripe with missing originals ----
+ * The calls above need every original.  With a disk out the caller has only
+ * rs_decode_device* / rs_repair_device*, which trust every present shard: one
+ * flipped bit in a present original, or in a recovery row the decode uses, is
+ * multiplied into every restored original and nothing reports it.  This call is
+ * the decode of such a stripe together with the locate's check of it.
+ *   The algebra is the locate's.  Any original_count shards of an MDS codeword are
+ * an information set.  With m originals missing, the present originals and m
+ * reference recovery rows are one; the remaining selected rows are parity over it.
+ * One corrupt shard of the set, wrong by e, contributes T[j][p] * e to check row j,
+ * with a coefficient matrix T that has no zero entry and no vanishing 2 x 2 minor.
+ *   Definitions.  m = the number of missing originals.  sel = the selected rows
+ * in increasing order, c = |sel|.  The reference rows are R = sel[0..m), the check
+ * rows K = sel[m..c).  F_b = stripe b's originals completed from R: the present
+ * rows as stored, the missing rows as rs_decode_device restores them with
+ * recovery_present = the indicator of R.  D_j = recovery_j ^ encode(F_b)_j.  The
+ * information position of an index p in [0, original_count) is original p where it
+ * is present, else reference row R[rank of p among the missing originals].
+ *   Arguments.  original_present: HOST mask of original_count bytes, required; ONE
+ * mask for every stripe of a batch, as rs_repair_device_batch; absent rows of
+ * d_original are never read.  recovery_check: HOST mask, NULL = every row, ONE mask
+ * for a batch; unselected rows are never read.  d_restored may be NULL (see below).
+ * Strides (0 = dense), alignment rules, the byte-wise path and the block and tail
+ * layout are those of the _strided / _batch calls; d_located and d_mismatch those of
+ * rs_locate_device[_batch].  Asynchronous on `stream`, scratch per (context, stream).
+ *   Result: after the call every byte of d_mismatch and every word of d_located is
+ * defined.  d_mismatch[b][j] is 1 exactly for j in K with D_j != 0; it is 0 for
+ * reference rows and unselected rows.  d_located[b] is
+ *   RS_LOCATE_CLEAN    no row of K differs.
+ *   RS_LOCATE_ROWS     some rows of K differ and some agree.  A single corrupt
+ *                      information shard would make every row of K differ, so that
+ *                      is ruled out; the flags name the differing rows.  NOT proven:
+ *                      that the information shards are intact.  Two or more corrupt
+ *                      ones can leave some check row matching by coincidence (their
+ *                      contributions cancel in that row), as rs_locate_device's
+ *                      section describes: a row that agrees vouches for no shard.
+ *   i in [0, original_count), original i present
+ *                      every row of K differs, and D_j = T[j][i] * e for one e per
+ *                      column, over every j in K.  Original i is the corrupt shard.
+ *   original_count + j, j in R
+ *                      the same statement for the information position that
+ *                      reference row j stands in.  Recovery row j is the corrupt shard.
+ *   RS_LOCATE_UNKNOWN  every row of K differs and no position explains it.
+ * The value depends on the stripe's bytes and the two masks alone, not on how it
+ * is computed.
+ *   Uniqueness and trust, on the [original_count + |K|, original_count] MDS code
+ * that the information shards and the rows of K are a word of.  With |K| >= 2 (the
+ * call takes no fewer) a named position is unique: two positions explaining the
+ * same D over two rows would need a vanishing 2 x 2 minor of T.  Up to |K| - 1
+ * corrupt shards among the original_count information shards and the rows of K are
+ * never attributed to a wrong position: that would need a vanishing |K| x |K| minor
+ * of [T | I], and an MDS code has none.  With exactly two check rows, two corrupt
+ * information shards CAN be attributed to a third.  Select three check rows where
+ * the stripe has them.
+ *   d_restored.  When it is non-NULL the missing originals' rows receive F_b's
+ * missing rows, byte-identical to rs_decode_device_batch with the R mask; present
+ * rows are never written.  It may alias d_original with equal strides (the
+ * repair's in-place argument: the rows written are exactly the rows never read;
+ * the later kernels read the recovery matrix and scratch).  The restored rows are
+ * trustworthy on CLEAN, and on ROWS with the caveat above.  After a located or
+ * UNKNOWN stripe they were decoded from a corrupt shard: re-run rs_repair_device*
+ * with the named shard absent.  Nothing is written but d_located, the flags and
+ * those rows.
+ *   m == 0: d_located and d_mismatch equal rs_locate_device_batch's for the same
+ * arguments, d_restored is untouched; the call delegates to the locate and shares
+ * its table.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * original_present, d_recovery, d_located or d_mismatch -> RS_ERR_INVALID_ARGUMENT;
+ * rs_validate; the row strides (restored_stride when d_restored is given); c < m ->
+ * RS_ERR_NOT_ENOUGH_SHARDS with the decode's counts (original_received_count =
+ * original_count - m, recovery_received_count = c); c < m + 2 ->
+ * RS_ERR_INVALID_ARGUMENT (decodable, but nothing is left to check with); the
+ * locate's shape bound.  stripes == 0: RS_OK, nothing launched or written, the
+ * context not touched.
+ *   Launches per group of stripes (a group: what rs_repair_device_batch runs as one
+ * launch; elsewhere one stripe), after the flags are zeroed: the repair with
+ * recovery_present = the indicator of R, its restored originals to d_restored or to
+ * per-stream scratch and its second output -- every recovery row outside R of the
+ * completed stripe, in one decode -- to a per-stream scratch matrix, the locate's
+ * `want`: no fill copy and no second encode.  Then k_verify_rows over K,
+ * k_locate_find and k_locate_confirm with the row list K and the table T, and
+ * k_locate_rename, one thread per stripe, which turns a located index p of a missing
+ * original into original_count + R[rank(p)] through an original_count-entry map.
+ *   The table.  log T[j][p], recovery_count x original_count uint16_t, every row
+ * outside R filled, is built by the first call with a given key on a stream: (rate,
+ * original_count, recovery_count, the original_present bytes, R).  Every row a call
+ * may check is filled, so the rows of K are not part of the key.  It is built over
+ * slabs of 256 positions as the locate's: k_coef_unit_degraded writes the element 1
+ * of position p into unit original p or into unit reference row R[rank(p)], the
+ * repair above runs on the unit stripe, k_coef_log_slab takes the logs.  It is kept
+ * with the stream's scratch until another key arrives or
+ * rs_release_stream_scratch frees it, and depends on neither the data nor
+ * d_restored.  The locate's table and the update's are different ones and are not
+ * disturbed.
+ *   Measured (tools/locate_degraded_time.py,
+ * profiles/locate_degraded/locate_degraded_time.txt; 1024:1024, every row selected,
+ * d_restored = d_original, us per call, median of five rounds of 50 back-to-back
+ * calls, the legs interleaved in one session; clean = no stripe differs, corrupt =
+ * one corrupt present original in every stripe, cold = the table rebuilt;
+ * yardstick = what a caller had before, rs_repair_device_batch with
+ * recovery_present = R in place and then rs_locate_device_batch under the mask K,
+ * both the parent commit's kernels, on the same clean / corrupt stripes -- where it
+ * can only answer UNKNOWN; spread = max - min of the yardstick's five rounds):
+ *     shape, m                clean    corrupt  cold     yardstick clean (spread) / corrupt (spread)
+ *     1 KiB, one stripe, 1     25.21    31.60   121.38    29.57 (1.93) /  35.19 (1.90)
+ *     1 KiB, one stripe, 16    25.53    32.52   124.57    31.37 (1.45) /  36.74 (1.18)
+ *     1 KiB, 64 stripes, 1    537.23   566.68   632.44   737.94 (0.96) / 743.27 (1.79)
+ *     1 KiB, 64 stripes, 16   557.29   585.47   655.76   754.96 (1.52) / 775.42 (1.62)
+ *     64 KiB, one stripe, 1   250.82   288.63   354.43   359.37 (1.22) / 374.87 (1.08)
+ *     64 KiB, one stripe, 16  292.35   335.73   401.35   396.53 (0.62) / 414.14 (0.56)
+ * The expectation was "the repair of the same pattern plus the locate's three small
+ * launches and one more", so within the yardstick's spread plus one launch floor
+ * (6.0-6.6 us, the shortest launch of the call by the library's events).  Every case
+ * lands within it, and below the yardstick: by 4.4 / 5.8 us on the single 1 KiB
+ * stripe, by 201 / 198 us on 64 stripes and by 109 / 104 us at 64 KiB, which is the
+ * yardstick's encode (k_mono<10> 10 / 209 us, three passes 111 us by the events) that
+ * the repair's second output makes unnecessary, less k_locate_rename (6.0-7.2 us).
+ * By the events a clean call is the repair (18.5 / 545 / 233 us at m = 1), k_verify_rows
+ * (6.4 / 30.7 / 26.6 us) and three launches at the floor.  A corrupt original in every
+ * stripe adds 6.4-7.0 / 28-29 / 38-43 us: the find's candidate path and the confirm, as
+ * in the locate.  The cold call adds 95-109 us: four slabs of (k_coef_unit_degraded, a
+ * one-stripe repair at 16-18 us, k_coef_log_slab).  A degraded stripe costs far more
+ * than a whole one (rs_locate_device_batch: 240 us for 64 clean stripes): the repair
+ * from m reference rows writes every other recovery row, where the locate's encode
+ * is one transform.  DESIGN.md "Degraded locate" has the rest.
+ *   Not covered: writing the correction back (a degraded heal); max_outliers; a
+ * mask per stripe; the host pipeline, the object API and the sharded classes. */
+rs_status rs_locate_device_degraded(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                    uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
+                                    const uint8_t *original_present, const void *d_recovery, uint64_t recovery_stride,
+                                    const uint8_t *recovery_check, void *d_restored, uint64_t restored_stride,
+                                    int32_t *d_located, uint8_t *d_mismatch, void *stream, rs_error *err);
+rs_status rs_locate_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                          uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                          const void *d_original, uint64_t original_stride,
+                                          uint64_t original_stripe_stride, const uint8_t *original_present,
+                                          const void *d_recovery, uint64_t recovery_stride,
+                                          uint64_t recovery_stripe_stride, const uint8_t *recovery_check,
+                                          void *d_restored, uint64_t restored_stride, uint64_t restored_stripe_stride,
+                                          int32_t *d_located, uint8_t *d_mismatch, void *stream, rs_error *err);
 
 /* ---- heal: fix what the locate found, in place, on the device ----
  * A scrub built from the calls above is three calls with a host round trip in the
@@ -858,7 +1001,8 @@ rs_status rs_locate_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t 
  * 103 us by the events): by 77 / 715 / 230 us for an original and 71 / 750 /
  * 143 us for a row, the rest being the synchronize, the two reads on the host and
  * the masks.  DESIGN.md "Heal" has the rest.
- *   Not covered: a mask per stripe; stripes with missing originals; the host
+ *   Not covered: a mask per stripe; stripes with missing originals
+ * (rs_locate_device_degraded above locates in those); the host
  * pipeline, the object API and the sharded classes. */
 #define RS_HEAL_ORIGINAL 1u /* a located original i: original_i ^= e */
 #define RS_HEAL_RECOVERY 2u /* a ROWS stripe: rewrite its differing selected rows */
@@ -989,7 +1133,8 @@ rs_status rs_heal_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_
  * decode's launches 212 us by the events), the rest being the synchronize, the
  * three reads on the host and the masks.  DESIGN.md "Robust heal" has the rest.
  *   Not covered: two or more corrupt originals; a mask per stripe; stripes with
- * missing originals; the host pipeline, the object API and the sharded classes. */
+ * missing originals (rs_locate_device_degraded above locates in those); the host
+ * pipeline, the object API and the sharded classes. */
 rs_status rs_heal_device_robust(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
                                 uint64_t shard_bytes, void *d_original, uint64_t original_stride, void *d_recovery,
                                 uint64_t recovery_stride, const uint8_t *recovery_check, uint32_t max_outliers,

@@ -192,6 +192,24 @@ struct LocateWs {
     uint64_t n = 0, m = 0;
 };
 
+// What rs_locate_device_degraded* keeps per stream (DESIGN.md "Degraded locate"):
+// the completed originals of a group of stripes (when the caller takes none) and
+// the group's `want` matrix -- the repair's two outputs --, the unit stripe of the
+// coefficient step, the table log T[j][p] over information positions with the key
+// it was built for, and the position map followed by the list of check rows on
+// the device with their host mirror.
+struct DegradedWs {
+    DevBuf unit, full, want, logs, d_lists;
+    PinnedBuf h_lists;
+    bool valid = false;  // `logs` holds the table of (high, n, m, present, ref)
+    int high = 0;
+    uint64_t n = 0, m = 0;
+    std::vector<uint8_t> present;  // the original_present bytes, as 0/1
+    std::vector<uint32_t> ref;     // the reference rows R
+    bool lists_valid = false;      // d_lists holds the map of (present, ref), then `check`
+    std::vector<uint32_t> check;   // the check rows K
+};
+
 // Device scratch of one stream's calls.  Calls on one stream execute in order,
 // so one workspace per (context, stream) makes concurrent calls on different
 // streams safe (rs_mi355x.h "Threading and streams").
@@ -202,10 +220,12 @@ struct Workspace {
     std::unique_ptr<UpdateWs> upd;  // rs_update_device*, made by the stream's first update
     std::unique_ptr<VerifyWs> ver;  // rs_verify_device*, made by the stream's first masked or unfused verify
     std::unique_ptr<LocateWs> loc;  // rs_locate_device*, made by the stream's first locate
+    std::unique_ptr<DegradedWs> deg;  // rs_locate_device_degraded*, made by the stream's first degraded locate
     void swap(Workspace &o) {
         upd.swap(o.upd);
         ver.swap(o.ver);
         loc.swap(o.loc);
+        deg.swap(o.deg);
         for (int k = 0; k < 4; ++k) buf[k].swap(o.buf[k]);
         rowinfo.swap(o.rowinfo);
         state.swap(o.state);
@@ -2201,6 +2221,151 @@ void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g,
     }
 }
 
+// ---- degraded locate (rs_locate_device_degraded*, DESIGN.md "Degraded locate") ----
+// What the call adds to a locate: the presence mask (m >= 1 originals missing), the
+// selected rows split into the m reference rows R and the check rows K, and where
+// the restored originals go (nullptr: per-stream scratch).
+struct DegradedCall {
+    const uint8_t *present;  // N bytes
+    std::vector<uint32_t> ref, check;
+    uint8_t *d_restored;
+    uint64_t restored_bstride;
+};
+
+// The position map and the check rows on the device: N words map[p] (p, or N + the
+// reference row standing in for the missing original p), then the |K| check rows.
+// Copied on `s` only when one of them changes.
+void degraded_lists(DegradedWs &d, uint64_t N, const std::vector<uint8_t> &present, const DegradedCall &C,
+                    hipStream_t s, const int32_t **d_map, const uint32_t **d_check) {
+    if (!(d.lists_valid && d.valid && d.check == C.check)) {
+        d.lists_valid = false;
+        const size_t words = N + C.check.size();
+        uint32_t *h = reinterpret_cast<uint32_t *>(d.h_lists.get(words * 4));
+        for (uint64_t p = 0, k = 0; p < N; ++p) h[p] = present[p] ? uint32_t(p) : uint32_t(N) + C.ref[k++];
+        std::copy(C.check.begin(), C.check.end(), h + N);
+        check(hipMemcpyAsync(d.d_lists.get(words * 4), h, words * 4, hipMemcpyHostToDevice, s));
+        d.h_lists.copied_on(s);
+        d.check = C.check;
+        d.lists_valid = true;
+    }
+    *d_map = static_cast<const int32_t *>(d.d_lists.p);
+    *d_check = static_cast<const uint32_t *>(d.d_lists.p) + N;
+}
+
+// log T[j][p] for every information position p and every recovery row j outside R
+// (the rows of R hold the sentinel), built on `s` unless the stream's workspace
+// holds the table of this (rate, N, M, presence mask, R) already: locate_table's
+// slabs, with the unit stripe over information positions and the degraded step --
+// the repair from R alone, whose second output is the slab's coefficients -- where
+// the locate has its encode.  Every row a call may check is filled, so the table
+// does not depend on which rows beyond R the mask selects.
+const uint16_t *degraded_table(rs_context *ctx, Workspace &ws, bool high, uint64_t N, uint64_t M,
+                               const DegradedCall &C, const uint8_t *ref_mask, hipStream_t s, const int32_t **d_map,
+                               const uint32_t **d_check) {
+    if (!ws.deg) ws.deg.reset(new DegradedWs);
+    DegradedWs &d = *ws.deg;
+    std::vector<uint8_t> present(N);
+    for (uint64_t i = 0; i < N; ++i) present[i] = C.present[i] != 0;
+    if (d.valid && d.high == int(high) && d.n == N && d.m == M && d.present == present && d.ref == C.ref) {
+        degraded_lists(d, N, present, C, s, d_map, d_check);
+        return static_cast<const uint16_t *>(d.logs.p);
+    }
+    d.valid = false;
+    if (!ctx->d_log) {  // as the context's first update
+        const rs::GfTables &T = rs::tables();
+        check(hipMalloc(&ctx->d_log, T.log.size() * 2));
+        check(hipMemcpy(ctx->d_log, T.log.data(), T.log.size() * 2, hipMemcpyHostToDevice));
+    }
+    degraded_lists(d, N, present, C, s, d_map, d_check);
+    const uint64_t W = 64 * ((std::min<uint64_t>(kLocateSlab, N) + 31) / 32);
+    uint8_t *unit = static_cast<uint8_t *>(d.unit.get((N + M) * W)), *unit_rec = unit + N * W;
+    uint8_t *full = static_cast<uint8_t *>(d.full.get(N * W));
+    uint8_t *coef = static_cast<uint8_t *>(d.want.get(M * W));
+    uint16_t *logs = static_cast<uint16_t *>(d.logs.get(round_up(M * N * 2, 4)));
+    check(hipMemsetAsync(coef, 0, M * W, s));  // the rows of R are never written: the sentinel
+    const Geom g = device_geom(W, 0, 0, 0, {unit, unit_rec, full, coef});
+    for (uint64_t i0 = 0; i0 < N; i0 += kLocateSlab) {
+        const uint32_t k = uint32_t(std::min<uint64_t>(kLocateSlab, N - i0));
+        check(hipMemsetAsync(unit, 0, (N + M) * W, s));
+        update_launch(s, k, [&] {
+            return rs::launch_locate_unit_degraded(unit, unit_rec, W, *d_map, uint32_t(N), uint32_t(i0), k, s);
+        });
+        repair_dev(ctx, ws, high, g, N, M, unit, C.present, unit_rec, ref_mask, full, coef, s);
+        update_launch(s, M * k * 4, [&] {
+            return rs::launch_locate_log(coef, W, uint32_t(M), uint32_t(i0), k, uint32_t(N), ctx->d_log, logs, s);
+        });
+    }
+    d.high = int(high), d.n = N, d.m = M;
+    d.present.swap(present);
+    d.ref = C.ref;
+    d.valid = true;
+    return logs;
+}
+
+// The caller has checked that an original is missing, that the mask selects two
+// rows more than are missing, the shape bound and that stripes > 0; g carries the
+// caller's strides of d_restored (where given) in its out fields.  Per group of
+// stripes -- what the repair runs as one launch, else one stripe -- the repair from
+// R alone (the restored originals to the caller or to scratch, every other
+// recovery row of the completed stripe to scratch: the locate's `want`), then the
+// locate's launches over K with the table over information positions, and the rename.
+void locate_degraded_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V,
+                         const DegradedCall &C, hipStream_t s) {
+    const uint32_t M = uint32_t(V.M), nsel = uint32_t(C.check.size());
+    std::vector<uint8_t> ref_mask(M, 0);
+    for (uint32_t j : C.ref) ref_mask[j] = 1;
+    const int32_t *d_map = nullptr;
+    const uint32_t *d_check = nullptr;
+    const uint16_t *logs = degraded_table(ctx, ws, high, V.N, V.M, C, ref_mask.data(), s, &d_map, &d_check);
+    DegradedWs &d = *ws.deg;
+    check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
+    // (decode_dev: does a batch of this shape decode as one launch?)
+    const DecodeRows dr = decode_rows(ctx, high, g, V.N, V.M);
+    const bool fused = use_mono(ctx, dr.u, g, 1) && rs::mono_staged(int(dr.u), 1) && dr.nd <= rs::kMonoFusedRows;
+    const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+    const uint64_t W = g.stride, group = fused ? kMaxBatchStripes : 1, held = std::min<uint64_t>(group, V.stripes);
+    uint8_t *want = static_cast<uint8_t *>(d.want.get(held * V.M * W));
+    uint8_t *full = C.d_restored ? nullptr : static_cast<uint8_t *>(d.full.get(held * V.N * W));
+    Geom gr = g;
+    gr.orig_bstride = V.orig_bstride;
+    gr.rec_bstride = V.rec_bstride;
+    gr.out2_stride = W;
+    gr.out2_bstride = V.M * W;
+    if (C.d_restored) {
+        gr.out_bstride = C.restored_bstride;
+    } else {
+        gr.out_stride = W;
+        gr.out_bstride = V.N * W;
+    }
+    for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
+        gr.stripes = uint32_t(std::min<uint64_t>(group, V.stripes - b0));
+        repair_dev(ctx, ws, high, gr, V.N, V.M, V.d_orig + b0 * V.orig_bstride, C.present,
+                   V.d_rec + b0 * V.rec_bstride, ref_mask.data(),
+                   C.d_restored ? C.d_restored + b0 * C.restored_bstride : full, want, s);
+        rs::VerifyRowsArgs R;
+        R.want = want, R.want_stride = W, R.want_bstride = V.M * W;
+        R.have = V.d_rec + b0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
+        R.rows = d_check, R.nrows = nsel, R.packs = g.packs, R.stripes = gr.stripes;
+        R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
+        R.fmt = g.fmt;
+        update_launch(s, 2 * uint64_t(nsel) * pack_bytes * gr.stripes, [&] { return rs::launch_verify_rows(R, s); });
+        rs::LocateArgs A;
+        A.want = R.want, A.want_stride = W, A.want_bstride = R.want_bstride;
+        A.have = R.have, A.have_stride = R.have_stride, A.have_bstride = R.have_bstride;
+        A.rows = d_check, A.nsel = nsel, A.packs = g.packs, A.stripes = gr.stripes;
+        A.N = uint32_t(V.N), A.M = M;
+        A.flags = R.flags, A.flag_bstride = V.M;
+        A.located = V.d_located + b0;
+        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
+        A.fmt = g.fmt;
+        update_launch(s, (V.M + 4) * uint64_t(gr.stripes), [&] { return rs::launch_locate_find(A, s); });
+        update_launch(s, 2 * uint64_t(nsel) * pack_bytes * gr.stripes, [&] { return rs::launch_locate_confirm(A, s); });
+        update_launch(s, 8 * uint64_t(gr.stripes), [&] {
+            return rs::launch_locate_rename(A.located, d_map, A.N, gr.stripes, s);
+        });
+    }
+}
+
 const char *hip_msg(hipError_t e) { return hipGetErrorString(e); }
 
 }  // namespace
@@ -3298,6 +3463,81 @@ rs_status rs_locate_device_robust(rs_context *ctx, rs_rate rate, uint64_t N, uin
                                   uint8_t *d_mismatch, uint8_t *d_outlier, void *stream, rs_error *err) {
     return rs_locate_device_robust_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0,
                                          recovery_check, max_outliers, d_located, d_mismatch, d_outlier, stream, err);
+}
+
+// ---- degraded locate: the locate of a stripe with missing originals (include/rs_mi355x.h) ----
+
+rs_status rs_locate_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                          uint64_t stripes, const void *d_orig, uint64_t orig_stride,
+                                          uint64_t orig_stripe_stride, const uint8_t *orig_present, const void *d_rec,
+                                          uint64_t rec_stride, uint64_t rec_stripe_stride,
+                                          const uint8_t *recovery_check, void *d_restored, uint64_t restored_stride,
+                                          uint64_t restored_stripe_stride, int32_t *d_located, uint8_t *d_mismatch,
+                                          void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !orig_present || !ptr_ok(d_rec) || !ptr_ok(d_located) || !ptr_ok(d_mismatch))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || (d_restored && !stride_ok(restored_stride, S)))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    uint64_t have_o = 0, nsel = M;
+    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
+    if (recovery_check) {
+        nsel = 0;
+        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
+    }
+    const uint64_t missing = N - have_o;
+    if (nsel < missing) {  // not decodable: the decode's error and counts
+        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
+        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = nsel;
+        return RS_ERR_NOT_ENOUGH_SHARDS;
+    }
+    // decodable, but a ratio needs two rows beyond the reference rows
+    if (nsel < missing + 2) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    // nothing missing: the locate itself (its table, its launches; d_restored untouched)
+    if (!missing)
+        return rs_locate_device_batch(ctx, rate, N, M, S, stripes, d_orig, orig_stride, orig_stripe_stride, d_rec,
+                                      rec_stride, rec_stripe_stride, recovery_check, d_located, d_mismatch, stream,
+                                      err);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        // (scratch rows are whole 64-byte blocks: neither stride of it forces the byte-wise path)
+        const uint64_t W = round_up(S, 64);
+        Geom g = d_restored ? device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored}, W)
+                            : device_geom(S, orig_stride, rec_stride, W, {d_orig, d_rec}, W);
+        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                      0, 0, recovery_check, d_mismatch},
+                     d_located};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        DegradedCall C;
+        C.present = orig_present;
+        C.d_restored = static_cast<uint8_t *>(d_restored);
+        C.restored_bstride = d_restored ? (restored_stripe_stride ? restored_stripe_stride : N * g.out()) : 0;
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride | C.restored_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        for (uint64_t j = 0; j < M; ++j)  // the selected rows in order: the first `missing` are R, the rest K
+            if (!recovery_check || recovery_check[j])
+                (C.ref.size() < missing ? C.ref : C.check).push_back(uint32_t(j));
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        locate_degraded_dev(ctx, sw.w, high != 0, g, V, C, s);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_locate_device_degraded(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                    const void *d_orig, uint64_t orig_stride, const uint8_t *orig_present,
+                                    const void *d_rec, uint64_t rec_stride, const uint8_t *recovery_check,
+                                    void *d_restored, uint64_t restored_stride, int32_t *d_located,
+                                    uint8_t *d_mismatch, void *stream, rs_error *err) {
+    return rs_locate_device_degraded_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, orig_present, d_rec,
+                                           rec_stride, 0, recovery_check, d_restored, restored_stride, 0, d_located,
+                                           d_mismatch, stream, err);
 }
 
 // ---- heal: the locate that also writes the correction (include/rs_mi355x.h) ----

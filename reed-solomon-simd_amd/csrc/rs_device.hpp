@@ -515,6 +515,18 @@ struct LocateArgs {
 hipError_t launch_locate_find(const LocateArgs &A, hipStream_t stream);
 hipError_t launch_locate_confirm(const LocateArgs &A, hipStream_t stream);
 
+// ---- degraded locate (rs_locate_device_degraded*, rs_locate.hip; DESIGN.md "Degraded locate") ----
+// map: N words, map[p] = p where original p is present, else N + the reference
+// recovery row that stands in for it (an information position either way).
+// launch_locate_unit_degraded is launch_locate_unit over information positions i0 ..
+// i0 + count - 1: element c of the shard map[i0 + c] names = 1, in zeroed unit
+// matrices of `stride` >= 64 * ceil(count / 32) bytes per row.  launch_locate_rename
+// (one thread per stripe, after the confirm) replaces located[b] = p in [0, N) by map[p].
+hipError_t launch_locate_unit_degraded(uint8_t *unit_orig, uint8_t *unit_rec, uint64_t stride, const int32_t *map,
+                                       uint32_t N, uint32_t i0, uint32_t count, hipStream_t stream);
+hipError_t launch_locate_rename(int32_t *located, const int32_t *map, uint32_t N, uint32_t stripes,
+                                hipStream_t stream);
+
 // ---- heal (rs_heal_device*, rs_locate.hip; DESIGN.md "Heal") -----------------
 // After the find (with `differ`) and the confirm of the same LocateArgs, while the
 // encode is still in `want`.  launch_heal (the confirm's grid) writes every

@@ -23,6 +23,14 @@
 //                      confirm's e, recomputed); a ROWS stripe within the caller's
 //                      threshold: its flagged selected rows copied from the scratch;
 //                      one action byte per stripe
+//
+// and of a degraded locate (rs_locate_device_degraded*, DESIGN.md "Degraded locate"),
+// whose `want` is the repair's second output and whose table is over information
+// positions (present originals and the reference recovery rows):
+//
+//   k_coef_unit_degraded   the unit stripe of a slab of information positions
+//   k_locate_rename        a located position that is a missing original: N + the
+//                          reference row that stands in for it
 #include <cstdio>
 
 #include "rs_device.hpp"
@@ -58,6 +66,28 @@ __global__ void k_coef_log_slab(const uint8_t *coef, uint64_t stride, uint32_t r
     if (c >= count || j >= rows) return;
     const uint8_t *p = coef + uint64_t(j) * stride + (c >> 5) * 64u + (c & 31u);
     logs[uint64_t(j) * pitch + i0 + c] = log_table[uint32_t(p[0]) | uint32_t(p[32]) << 8];
+}
+
+// The unit stripe of a degraded locate's slab (rs_locate_device_degraded*, DESIGN.md
+// "Degraded locate"): element c = 1 in the shard that information position i0 + c
+// lives in -- map[p] = p: original p; N + j: recovery row j, which stands in for the
+// missing original p.  The rows of both unit matrices are zeroed ahead of it.
+__global__ void k_coef_unit_degraded(uint8_t *unit_orig, uint8_t *unit_rec, uint64_t stride, const int32_t *map,
+                                     uint32_t N, uint32_t i0, uint32_t count) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= count) return;
+    const uint32_t t = uint32_t(map[i0 + c]);
+    uint8_t *row = t < N ? unit_orig + uint64_t(t) * stride : unit_rec + uint64_t(t - N) * stride;
+    row[(c >> 5) * 64u + (c & 31u)] = 1;
+}
+
+// After the confirm of a degraded locate: a located information position that is a
+// missing original becomes N + the recovery row standing in for it.  One thread per stripe.
+__global__ void k_locate_rename(int32_t *located, const int32_t *map, uint32_t N, uint32_t stripes) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= stripes) return;
+    const int32_t p = located[b];
+    if (p >= 0 && uint32_t(p) < N) located[b] = map[p];
 }
 
 // D of pack io of row j of stripe-relative bases want / have.
@@ -238,6 +268,23 @@ hipError_t launch_locate_unit(uint8_t *unit, uint64_t stride, uint32_t i0, uint3
     if (!count) return hipSuccess;
     k_coef_unit_slab<<<dim3((count + 255) / 256), 256, 0, s>>>(unit, stride, i0, count);
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_coef_unit_slab");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_unit_degraded(uint8_t *unit_orig, uint8_t *unit_rec, uint64_t stride, const int32_t *map,
+                                       uint32_t N, uint32_t i0, uint32_t count, hipStream_t s) {
+    if (!count) return hipSuccess;
+    if (!map || uint64_t(i0) + count > N || stride < 64 * ((uint64_t(count) + 31) / 32)) return hipErrorInvalidValue;
+    k_coef_unit_degraded<<<dim3((count + 255) / 256), 256, 0, s>>>(unit_orig, unit_rec, stride, map, N, i0, count);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_coef_unit_degraded");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_rename(int32_t *located, const int32_t *map, uint32_t N, uint32_t stripes, hipStream_t s) {
+    if (!stripes) return hipSuccess;
+    if (!located || !map) return hipErrorInvalidValue;
+    k_locate_rename<<<dim3((stripes + 255) / 256), 256, 0, s>>>(located, map, N, stripes);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_rename");
     return hipGetLastError();
 }
 

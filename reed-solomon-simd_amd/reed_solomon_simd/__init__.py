@@ -127,6 +127,10 @@ _sig("rs_locate_device_robust", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _v
      ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_locate_device_robust_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
+_sig("rs_locate_device_degraded", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, ctypes.c_char_p, _vp, _u64,
+     ctypes.c_char_p, _vp, _u64, _vp, _vp, _vp, _E)
+_sig("rs_locate_device_degraded_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, ctypes.c_char_p, _vp,
+     _u64, _u64, ctypes.c_char_p, _vp, _u64, _u64, _vp, _vp, _vp, _E)
 _sig("rs_heal_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, ctypes.c_uint32,
      ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_heal_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
@@ -1316,6 +1320,85 @@ def locate_device_robust_batch(original_count: int, recovery_count: int, shard_b
                                               rows, t, _ptr(d_located), _ptr(d_mismatch), _ptr(d_outlier),
                                               _stream(stream), ctypes.byref(err)), err)
     return d_located, d_mismatch, d_outlier
+
+
+def _degraded_masks(original_present, original_count, recovery_rows, recovery_count):
+    present = _check_mask(present_mask(original_present), original_count, "original_present")
+    rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
+                                                          "recovery_rows")
+    m = sum(1 for b in present if not b)
+    c = recovery_count if rows is None else sum(1 for b in rows if b)
+    if m <= c < m + 2:  # (c < m: the library's NotEnoughShards, with its counts)
+        raise ValueError(f"recovery_rows: {m} missing originals take {m} of the {c} selected recovery rows as "
+                         f"reference rows; a locate needs two more at least")
+    return present, rows
+
+
+def locate_device_degraded(original_count: int, recovery_count: int, shard_bytes: int, d_original, original_present,
+                           d_recovery, recovery_rows=None, d_restored=None, d_located=None, d_mismatch=None,
+                           stream=None, rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """locate_device on a stripe with missing originals (rs_locate_device_degraded).  With m
+    originals missing (original_present: original_count flags, absent rows are never read), the
+    first m selected recovery rows are reference rows -- the missing originals are decoded from
+    them and the present originals -- and the remaining selected rows are checked against the
+    completed stripe.  Returns (located, mismatch): located is LOCATE_CLEAN, LOCATE_ROWS, the index
+    i of the corrupt present original, original_count + j for a corrupt reference row j, or
+    LOCATE_UNKNOWN; mismatch [recovery_count] flags the check rows that differ.  d_restored
+    (optional, [original_count, shard_bytes]; may be d_original) receives the restored originals
+    in its missing rows, as decode_device from the reference rows alone writes them; after a
+    located or UNKNOWN stripe they came from a corrupt shard: repair again with it absent.  Needs
+    m + 2 selected rows, better m + 3.  Asynchronous on `stream`."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    present, rows = _degraded_masks(original_present, original_count, recovery_rows, recovery_count)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    if d_restored is not None:
+        _check_matrix(d_restored, original_count, shard_bytes, "d_restored")
+    d_located = _check_located(d_located, (1,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_locate_device_degraded(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
+                                          _ptr(d_original), _row_stride(d_original), present, _ptr(d_recovery),
+                                          _row_stride(d_recovery), rows,
+                                          None if d_restored is None else _ptr(d_restored),
+                                          0 if d_restored is None else _row_stride(d_restored), _ptr(d_located),
+                                          _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch
+
+
+def locate_device_degraded_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original,
+                                 original_present, d_recovery, recovery_rows=None, d_restored=None, d_located=None,
+                                 d_mismatch=None, stream=None, rate_: int = RATE_DEFAULT,
+                                 ctx: Optional[Context] = None):
+    """locate_device_degraded on a batch of stripes sharing ONE presence mask and ONE row mask
+    (rs_locate_device_degraded_batch); tensors [stripes, rows, shard_bytes].  Returns (located
+    [stripes], mismatch [stripes, recovery_count])."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    present, rows = _degraded_masks(original_present, original_count, recovery_rows, recovery_count)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    x_row = x_b = 0
+    if d_restored is not None:
+        _check_matrix(d_restored, original_count, shard_bytes, "d_restored", 3)
+        if d_restored.shape[0] != n:
+            raise ValueError("original and restored batches differ in stripe count")
+        x_row, x_b = _batch_strides(d_restored)
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_locate_device_degraded_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                                d_original.data_ptr(), o_row, o_b, present, d_recovery.data_ptr(),
+                                                r_row, r_b, rows,
+                                                None if d_restored is None else d_restored.data_ptr(), x_row, x_b,
+                                                _ptr(d_located), _ptr(d_mismatch), _stream(stream),
+                                                ctypes.byref(err)), err)
+    return d_located, d_mismatch
 
 
 HEAL_ORIGINAL = 1  # RS_HEAL_ORIGINAL (include/rs_mi355x.h)
