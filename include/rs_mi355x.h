@@ -902,7 +902,8 @@ rs_status rs_locate_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t 
  * from m reference rows writes every other recovery row, where the locate's encode
  * is one transform.  DESIGN.md "Degraded locate" has the rest.
  *   Not covered: writing the correction back (a degraded heal); max_outliers; a
- * mask per stripe; the host pipeline, the object API and the sharded classes. */
+ * mask per stripe; the host pipeline, the object API and the sharded classes.
+ * (rs_heal_device_degraded below is that heal.) */
 rs_status rs_locate_device_degraded(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
                                     uint64_t shard_bytes, const void *d_original, uint64_t original_stride,
                                     const uint8_t *original_present, const void *d_recovery, uint64_t recovery_stride,
@@ -1147,6 +1148,151 @@ rs_status rs_heal_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t or
                                       const uint8_t *recovery_check, uint32_t max_outliers, uint32_t mode,
                                       uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_outlier,
                                       uint8_t *d_action, void *stream, rs_error *err);
+
+/* ---- degraded heal: fix what the degraded locate found, in place ----
+ * rs_locate_device_degraded names the corrupt information shard of a stripe that
+ * has originals missing, and leaves the caller to act on it: a synchronize, a host
+ * read of d_located, masks per stripe and rs_repair_device_batch_masks, a second
+ * full decode of every damaged stripe -- on the stripes where a disk is already
+ * out and every restored original carries the error.  Yet at the end of the
+ * degraded locate everything a heal needs is on the device: the located position
+ * q, e = D_j0 / T[j0][q] per column (j0 = K[0]), which the confirm has just formed,
+ * the completed stripe's recovery rows in per-stream scratch, and the restored
+ * originals in d_restored.  The missing ingredient is U[p][q], the element that the
+ * decode from R puts into restored original p when information position q holds
+ * the element 1 and every other one holds zero: the decode is linear per column,
+ * so with shard q wrong by e
+ *     clean shard q            = stored shard q ^ e
+ *     clean missing original p = F_b[p] ^ U[p][q] * e.
+ * No U[p][q] is zero (the codeword with 1 at q and 0 at the other original_count - 1
+ * information positions would have original_count zeros; an MDS code allows one
+ * fewer).  This call is the degraded locate followed by one more launch per group of
+ * stripes that writes those: asynchronous on `stream`, no host synchronization, no
+ * second decode.  Notation is rs_locate_device_degraded's.
+ *   Arguments.  Argument order, the two HOST masks (ONE of each for every stripe of
+ * a batch), strides (0 = dense), alignment rules, the byte-wise path and the block
+ * and tail layout are those of rs_locate_device_degraded[_batch]; mode, max_rows and
+ * d_action those of rs_heal_device.  d_original and d_recovery are written in place.
+ * d_restored is REQUIRED; it may alias d_original with equal strides.
+ *   Result.  d_located and d_mismatch hold exactly what
+ * rs_locate_device_degraded_batch writes for the same arguments: they describe the
+ * stripe AS FOUND.  Every byte of d_action is defined:
+ *   RS_HEAL_ORIGINAL  d_located[b] = i < original_count (a present original) and mode
+ *                     has the bit: original i has become original_i ^ e, and every
+ *                     missing original's row p of d_restored F_b[p] ^ U[p][i] * e.
+ *                     Only shard_bytes bytes per row are written.
+ *   RS_HEAL_RECOVERY  d_located[b] = original_count + j (a reference row) and mode has
+ *                     the bit: recovery row j has become recovery_j ^ e, and the
+ *                     restored rows are corrected the same way with that row's
+ *                     position.  Or d_located[b] = RS_LOCATE_ROWS, mode has the bit
+ *                     and at most max_rows rows of K differ: each differing row of K
+ *                     has become the encode of F_b; the restored rows stay F_b's.
+ *   0                 anything else (CLEAN, UNKNOWN, ROWS above the threshold, an
+ *                     outcome whose mode bit is off): the three matrices end up
+ *                     exactly as rs_locate_device_degraded_batch leaves them -- the
+ *                     missing rows of d_restored are F_b's, nothing else is written.
+ * The mode bits say which matrix the call may write: RS_HEAL_ORIGINAL d_original,
+ * RS_HEAL_RECOVERY d_recovery (d_restored is written by every call).
+ *   After a located stripe is healed every selected row, R and K alike, agrees
+ * with the encode of the now complete originals; if that shard was the only
+ * damage, d_original with d_restored's rows, and d_recovery, are byte-identical to
+ * the clean stripe; a second call on the result reports RS_LOCATE_CLEAN with action
+ * 0 and rewrites the missing rows with the same bytes.
+ *   CAVEAT (the heal's, carried over): a ROWS stripe does not prove the information
+ * shards intact; RS_HEAL_RECOVERY can make check rows consistent with CORRUPT ones.
+ * Keep max_rows well below half of |K|.
+ *   m == 0: the call delegates to rs_heal_device_batch and leaves d_restored
+ * untouched.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * original_present, d_recovery, d_restored, d_located, d_mismatch or d_action ->
+ * RS_ERR_INVALID_ARGUMENT; rs_validate; the three row strides; mode == 0 or a bit
+ * outside the two -> RS_ERR_INVALID_ARGUMENT; c < m -> RS_ERR_NOT_ENOUGH_SHARDS with
+ * the decode's counts; c < m + 3 -> RS_ERR_INVALID_ARGUMENT (the call writes on the
+ * evidence of a location, so it takes three check rows: with two, two corrupt
+ * information shards can be attributed to a third, see the degraded locate); the
+ * locate's shape bound.  stripes == 0: RS_OK, nothing launched or written, the
+ * context not touched.  The matrices must not overlap one another or the three
+ * outputs, d_restored on d_original excepted.
+ *   Launches: the degraded locate's, group of stripes by group of stripes;
+ * k_locate_find also stores each stripe's count of differing rows; and one
+ * k_heal_degraded per group directly after that group's k_locate_confirm and before
+ * its k_locate_rename, while d_located[b] is still the information position and the
+ * group's `want` is still in scratch.  Its grid is the confirm's pack tiles x row
+ * groups over max(m, |K|) rows x stripes; a located stripe's restored rows are dealt
+ * round the row groups; workgroups of a stripe with nothing to do, and row groups
+ * with no row, leave at once.
+ *   The table log U[r][q], m x original_count uint16_t (row r: the r-th missing
+ * original), is kept beside log T under the same key.  It comes from the first output
+ * of the unit stripe's repair, which the degraded locate's table build discards: one
+ * k_coef_log_rows per slab right after that slab's repair, and only when a heal asks
+ * for it -- rs_locate_device_degraded launches exactly what it did.  A degraded locate
+ * after a heal on the stream finds T.  A heal after a degraded locate builds BOTH
+ * tables again: the slab's repair, which is the cost, yields both at once.
+ *   Measured (tools/heal_degraded_time.py, profiles/heal_degraded/heal_degraded_time.txt;
+ * 1024:1024, every row, both mode bits, max_rows 16, d_restored = d_original, us per
+ * call, median of five rounds of 50 back-to-back calls, the legs interleaved in one
+ * session; locate = rs_locate_device_degraded_batch on the clean batch, spread = max -
+ * min of its five rounds, in brackets the same leg on the parent commit's build in
+ * the same session; corrupt = one corrupt present original in EVERY stripe; scrub =
+ * what a caller had before: the degraded locate, a synchronize, a host read of
+ * d_located, the masks and rs_repair_device_batch_masks with the named shard absent;
+ * the corrupt heal and scrub legs net of the 4.6-5.6 us launch that puts the damage
+ * back before each call):
+ *     shape, m                locate (parent) spread  heal clean  locate corrupt  heal corrupt  scrub corrupt
+ *     1 KiB, one stripe, 1     26.40  (29.17)   2.25     33.22        34.88           36.30        104.36
+ *     1 KiB, one stripe, 16    28.17  (29.51)   5.69     33.03        35.00           36.33        110.16
+ *     1 KiB, 64 stripes, 1    536.28 (535.56)   1.27    539.41       565.45          572.13       1309.73
+ *     1 KiB, 64 stripes, 16   559.68 (559.08)   1.36    562.43       589.59          595.57       1335.48
+ *     64 KiB, one stripe, 1   249.84 (249.30)   3.16    252.35       291.75          296.94        506.52
+ *     64 KiB, one stripe, 16  292.48 (292.32)   0.61    294.94       336.98          343.61        595.23
+ * The expectation was "the degraded locate on the same input plus one launch": on a
+ * clean batch within the locate's spread plus one launch floor (6.0-6.2 us, the
+ * shortest launch of the call by the library's events), on a damaged stripe a
+ * read-modify-write of m + 1 rows more.  On 64 stripes and at 64 KiB every clean case
+ * lands well within it: +3.1 / +2.7 and +2.5 / +2.5 us, k_heal_degraded at 6.0-6.5 us
+ * between two of the library's events.  The single 1 KiB stripe is bound by the host's
+ * launch rate (six launches in 26-28 us), and there the seventh launch costs +6.8 /
+ * +4.9 us: within the bound as the tool computes it, but only because that leg's rounds
+ * spread 2.3-5.7 us.  A second session of the same build, right after the whole test
+ * suite (heal_degraded_time_after_suite.txt), read +8.2 / +8.7 us there, the second 1.0
+ * us OUTSIDE its bound of 7.7 us; its other four cases read +0.8 to +3.3 us.  So at one
+ * small stripe a clean heal costs the locate plus 5-9 us, about one launch slot of the
+ * host's, not the 2-3 us of the larger cases -- as rs_heal_device_robust measured on
+ * the same shape.  The locate legs of this build and of the parent's agree within
+ * 0.2-0.7 us (1.3-2.8 us on the single stripe, inside that leg's spread): the locate
+ * launches what it did.  A healed original costs +1.4 / +1.3 us over the locate's own
+ * corrupt case on the single stripe, +6.7 / +6.0 us on 64 stripes and +5.2 / +6.6 us at
+ * 64 KiB (k_heal_degraded 6.5 / 9.6-8.0 / 7.6 us by the events): the restored rows of a
+ * located stripe are dealt round the grid's row groups, so that m = 16 under 1008
+ * check rows spreads over 16 workgroups per pack tile and costs what m = 1 does.
+ * (The corrupt heal's figures are a difference: each call is timed behind the launch
+ * that puts the damage back, and that launch's median, 4.6-5.6 us timed alone with
+ * rounds spreading 0.1-2.0 us, is taken off; on the single stripe it may also overlap
+ * the call's own launches on the host.  So these deltas are good to about 2 us, and
+ * the single stripe's +1.4 / +1.3 us says "at most a few us", no more; the kernel's
+ * device time by the events is the direct figure.)
+ * Both beat the scrub by more than its second decode (k_mono_repair_masks 19.5 / 606-610 us, the 64
+ * KiB decode's launches 169 / 219 us by the events): by 68 / 74 us (2.9 / 3.0 times) on
+ * the single stripe, 738 / 740 us (2.3 / 2.2 times) on 64 stripes and 210 / 252 us (1.7
+ * times) at 64 KiB, the rest being the synchronize, the read and the masks.
+ * DESIGN.md "Degraded heal" has the rest.
+ *   Not covered: max_outliers for degraded stripes; a mask per stripe; filling
+ * unselected recovery rows; the host pipeline, the object API and the sharded
+ * classes. */
+rs_status rs_heal_device_degraded(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
+                                  uint64_t shard_bytes, void *d_original, uint64_t original_stride,
+                                  const uint8_t *original_present, void *d_recovery, uint64_t recovery_stride,
+                                  const uint8_t *recovery_check, void *d_restored, uint64_t restored_stride,
+                                  uint32_t mode, uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch,
+                                  uint8_t *d_action, void *stream, rs_error *err);
+rs_status rs_heal_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                        uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                        void *d_original, uint64_t original_stride, uint64_t original_stripe_stride,
+                                        const uint8_t *original_present, void *d_recovery, uint64_t recovery_stride,
+                                        uint64_t recovery_stripe_stride, const uint8_t *recovery_check,
+                                        void *d_restored, uint64_t restored_stride, uint64_t restored_stripe_stride,
+                                        uint32_t mode, uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch,
+                                        uint8_t *d_action, void *stream, rs_error *err);
 
 /* ---- host-memory pipeline (shards arrive from a socket or file) ----
  * h_original (original_count x shard_bytes) and h_recovery (recovery_count x

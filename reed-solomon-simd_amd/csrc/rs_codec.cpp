@@ -196,12 +196,16 @@ struct LocateWs {
 // the completed originals of a group of stripes (when the caller takes none) and
 // the group's `want` matrix -- the repair's two outputs --, the unit stripe of the
 // coefficient step, the table log T[j][p] over information positions with the key
-// it was built for, and the position map followed by the list of check rows on
-// the device with their host mirror.
+// it was built for, and the position map followed by the list of check rows and
+// the list of missing originals on the device with their host mirror.
+// rs_heal_device_degraded* adds the table log U[r][q] under the same key and a
+// group's counts of differing rows.
 struct DegradedWs {
     DevBuf unit, full, want, logs, d_lists;
+    DevBuf logu, differ;
     PinnedBuf h_lists;
     bool valid = false;  // `logs` holds the table of (high, n, m, present, ref)
+    bool u_valid = false;  // and `logu` that key's log U (only a heal builds it)
     int high = 0;
     uint64_t n = 0, m = 0;
     std::vector<uint8_t> present;  // the original_present bytes, as 0/1
@@ -2233,15 +2237,20 @@ struct DegradedCall {
 };
 
 // The position map and the check rows on the device: N words map[p] (p, or N + the
-// reference row standing in for the missing original p), then the |K| check rows.
-// Copied on `s` only when one of them changes.
+// reference row standing in for the missing original p), then the |K| check rows,
+// then the m missing originals in order (a heal's).  Copied on `s` only when one of
+// them changes.
 void degraded_lists(DegradedWs &d, uint64_t N, const std::vector<uint8_t> &present, const DegradedCall &C,
                     hipStream_t s, const int32_t **d_map, const uint32_t **d_check) {
     if (!(d.lists_valid && d.valid && d.check == C.check)) {
         d.lists_valid = false;
-        const size_t words = N + C.check.size();
+        const size_t words = N + C.check.size() + C.ref.size();
         uint32_t *h = reinterpret_cast<uint32_t *>(d.h_lists.get(words * 4));
-        for (uint64_t p = 0, k = 0; p < N; ++p) h[p] = present[p] ? uint32_t(p) : uint32_t(N) + C.ref[k++];
+        uint32_t *miss = h + N + C.check.size();
+        for (uint64_t p = 0, k = 0; p < N; ++p) {
+            h[p] = present[p] ? uint32_t(p) : uint32_t(N) + C.ref[k];
+            if (!present[p]) miss[k++] = uint32_t(p);
+        }
         std::copy(C.check.begin(), C.check.end(), h + N);
         check(hipMemcpyAsync(d.d_lists.get(words * 4), h, words * 4, hipMemcpyHostToDevice, s));
         d.h_lists.copied_on(s);
@@ -2258,19 +2267,23 @@ void degraded_lists(DegradedWs &d, uint64_t N, const std::vector<uint8_t> &prese
 // slabs, with the unit stripe over information positions and the degraded step --
 // the repair from R alone, whose second output is the slab's coefficients -- where
 // the locate has its encode.  Every row a call may check is filled, so the table
-// does not depend on which rows beyond R the mask selects.
+// does not depend on which rows beyond R the mask selects.  need_u (a heal): the
+// slab's first output, the restored originals of the unit stripe, becomes log U[r][q]
+// by one more log launch per slab; a table built without it is built again, both
+// halves (the slab's repair, which is the cost, yields both at once).
 const uint16_t *degraded_table(rs_context *ctx, Workspace &ws, bool high, uint64_t N, uint64_t M,
                                const DegradedCall &C, const uint8_t *ref_mask, hipStream_t s, const int32_t **d_map,
-                               const uint32_t **d_check) {
+                               const uint32_t **d_check, bool need_u = false) {
     if (!ws.deg) ws.deg.reset(new DegradedWs);
     DegradedWs &d = *ws.deg;
     std::vector<uint8_t> present(N);
     for (uint64_t i = 0; i < N; ++i) present[i] = C.present[i] != 0;
-    if (d.valid && d.high == int(high) && d.n == N && d.m == M && d.present == present && d.ref == C.ref) {
+    if (d.valid && d.high == int(high) && d.n == N && d.m == M && d.present == present && d.ref == C.ref &&
+        (d.u_valid || !need_u)) {
         degraded_lists(d, N, present, C, s, d_map, d_check);
         return static_cast<const uint16_t *>(d.logs.p);
     }
-    d.valid = false;
+    d.valid = d.u_valid = false;
     if (!ctx->d_log) {  // as the context's first update
         const rs::GfTables &T = rs::tables();
         check(hipMalloc(&ctx->d_log, T.log.size() * 2));
@@ -2282,6 +2295,13 @@ const uint16_t *degraded_table(rs_context *ctx, Workspace &ws, bool high, uint64
     uint8_t *full = static_cast<uint8_t *>(d.full.get(N * W));
     uint8_t *coef = static_cast<uint8_t *>(d.want.get(M * W));
     uint16_t *logs = static_cast<uint16_t *>(d.logs.get(round_up(M * N * 2, 4)));
+    const uint32_t m = uint32_t(C.ref.size());
+    uint16_t *logu = nullptr;
+    const uint32_t *d_miss = nullptr;  // the missing originals, behind K in d_lists
+    if (need_u) {
+        logu = static_cast<uint16_t *>(d.logu.get(round_up(uint64_t(m) * N * 2, 4)));
+        d_miss = *d_check + C.check.size();
+    }
     check(hipMemsetAsync(coef, 0, M * W, s));  // the rows of R are never written: the sentinel
     const Geom g = device_geom(W, 0, 0, 0, {unit, unit_rec, full, coef});
     for (uint64_t i0 = 0; i0 < N; i0 += kLocateSlab) {
@@ -2294,11 +2314,16 @@ const uint16_t *degraded_table(rs_context *ctx, Workspace &ws, bool high, uint64
         update_launch(s, M * k * 4, [&] {
             return rs::launch_locate_log(coef, W, uint32_t(M), uint32_t(i0), k, uint32_t(N), ctx->d_log, logs, s);
         });
+        if (!need_u) continue;
+        update_launch(s, uint64_t(m) * k * 4, [&] {
+            return rs::launch_locate_log_rows(full, W, d_miss, m, uint32_t(i0), k, uint32_t(N), ctx->d_log, logu, s);
+        });
     }
     d.high = int(high), d.n = N, d.m = M;
     d.present.swap(present);
     d.ref = C.ref;
     d.valid = true;
+    d.u_valid = need_u;
     return logs;
 }
 
@@ -2309,14 +2334,17 @@ const uint16_t *degraded_table(rs_context *ctx, Workspace &ws, bool high, uint64
 // R alone (the restored originals to the caller or to scratch, every other
 // recovery row of the completed stripe to scratch: the locate's `want`), then the
 // locate's launches over K with the table over information positions, and the rename.
+// With a heal (rs_heal_device_degraded*; C.d_restored given), k_heal_degraded runs
+// between the confirm and the rename, inside the loop: located[b] is still the
+// information position and the group's `want` is still in scratch.
 void locate_degraded_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V,
-                         const DegradedCall &C, hipStream_t s) {
+                         const DegradedCall &C, hipStream_t s, const HealCall *H = nullptr) {
     const uint32_t M = uint32_t(V.M), nsel = uint32_t(C.check.size());
     std::vector<uint8_t> ref_mask(M, 0);
     for (uint32_t j : C.ref) ref_mask[j] = 1;
     const int32_t *d_map = nullptr;
     const uint32_t *d_check = nullptr;
-    const uint16_t *logs = degraded_table(ctx, ws, high, V.N, V.M, C, ref_mask.data(), s, &d_map, &d_check);
+    const uint16_t *logs = degraded_table(ctx, ws, high, V.N, V.M, C, ref_mask.data(), s, &d_map, &d_check, H != nullptr);
     DegradedWs &d = *ws.deg;
     check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
     // (decode_dev: does a batch of this shape decode as one launch?)
@@ -2326,6 +2354,7 @@ void locate_degraded_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &
     const uint64_t W = g.stride, group = fused ? kMaxBatchStripes : 1, held = std::min<uint64_t>(group, V.stripes);
     uint8_t *want = static_cast<uint8_t *>(d.want.get(held * V.M * W));
     uint8_t *full = C.d_restored ? nullptr : static_cast<uint8_t *>(d.full.get(held * V.N * W));
+    uint32_t *differ = H ? static_cast<uint32_t *>(d.differ.get(held * 4)) : nullptr;
     Geom gr = g;
     gr.orig_bstride = V.orig_bstride;
     gr.rec_bstride = V.rec_bstride;
@@ -2349,7 +2378,7 @@ void locate_degraded_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &
         R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
         R.fmt = g.fmt;
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * gr.stripes, [&] { return rs::launch_verify_rows(R, s); });
-        rs::LocateArgs A;
+        rs::HealDegradedArgs A;  // the locate's kernels take its LocateArgs
         A.want = R.want, A.want_stride = W, A.want_bstride = R.want_bstride;
         A.have = R.have, A.have_stride = R.have_stride, A.have_bstride = R.have_bstride;
         A.rows = d_check, A.nsel = nsel, A.packs = g.packs, A.stripes = gr.stripes;
@@ -2358,8 +2387,22 @@ void locate_degraded_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &
         A.located = V.d_located + b0;
         A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
         A.fmt = g.fmt;
+        A.differ = differ;
         update_launch(s, (V.M + 4) * uint64_t(gr.stripes), [&] { return rs::launch_locate_find(A, s); });
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * gr.stripes, [&] { return rs::launch_locate_confirm(A, s); });
+        if (H) {
+            A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
+            A.rec = H->d_rec + b0 * V.rec_bstride;
+            A.mode = H->mode, A.max_rows = H->max_rows;
+            A.action = H->d_action + b0;
+            A.map = d_map, A.miss = d_check + nsel, A.m = uint32_t(C.ref.size());
+            A.logu = static_cast<const uint16_t *>(d.logu.p);
+            A.restored = C.d_restored + b0 * C.restored_bstride;
+            A.restored_stride = g.out(), A.restored_bstride = C.restored_bstride;
+            // a stripe with nothing to heal costs a word; a located one two per restored row
+            // and three for its shard, a ROWS one two per rewritten row
+            update_launch(s, 5 * uint64_t(gr.stripes), [&] { return rs::launch_heal_degraded(A, s); });
+        }
         update_launch(s, 8 * uint64_t(gr.stripes), [&] {
             return rs::launch_locate_rename(A.located, d_map, A.N, gr.stripes, s);
         });
@@ -3538,6 +3581,85 @@ rs_status rs_locate_device_degraded(rs_context *ctx, rs_rate rate, uint64_t N, u
     return rs_locate_device_degraded_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, orig_present, d_rec,
                                            rec_stride, 0, recovery_check, d_restored, restored_stride, 0, d_located,
                                            d_mismatch, stream, err);
+}
+
+// ---- degraded heal: the degraded locate that also writes the correction (include/rs_mi355x.h) ----
+
+rs_status rs_heal_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                        uint64_t stripes, void *d_orig, uint64_t orig_stride,
+                                        uint64_t orig_stripe_stride, const uint8_t *orig_present, void *d_rec,
+                                        uint64_t rec_stride, uint64_t rec_stripe_stride,
+                                        const uint8_t *recovery_check, void *d_restored, uint64_t restored_stride,
+                                        uint64_t restored_stripe_stride, uint32_t mode, uint32_t max_rows,
+                                        int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action, void *stream,
+                                        rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !orig_present || !ptr_ok(d_rec) || !ptr_ok(d_restored) || !ptr_ok(d_located) ||
+        !ptr_ok(d_mismatch) || !ptr_ok(d_action))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    uint64_t have_o = 0, nsel = M;
+    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
+    if (recovery_check) {
+        nsel = 0;
+        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
+    }
+    const uint64_t missing = N - have_o;
+    if (nsel < missing) {  // not decodable: the decode's error and counts
+        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
+        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = nsel;
+        return RS_ERR_NOT_ENOUGH_SHARDS;
+    }
+    // three check rows to write on the evidence of a location (with two, two corrupt
+    // information shards can be attributed to a third)
+    if (nsel < missing + 3) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    // nothing missing: the heal itself (its table, its launches; d_restored untouched)
+    if (!missing)
+        return rs_heal_device_batch(ctx, rate, N, M, S, stripes, d_orig, orig_stride, orig_stripe_stride, d_rec,
+                                    rec_stride, rec_stripe_stride, recovery_check, mode, max_rows, d_located,
+                                    d_mismatch, d_action, stream, err);
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        // (as rs_locate_device_degraded_batch, d_restored given)
+        const uint64_t W = round_up(S, 64);
+        Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored}, W);
+        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                      0, 0, recovery_check, d_mismatch},
+                     d_located};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        DegradedCall C;
+        C.present = orig_present;
+        C.d_restored = static_cast<uint8_t *>(d_restored);
+        C.restored_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride | C.restored_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        for (uint64_t j = 0; j < M; ++j)  // the selected rows in order: the first `missing` are R, the rest K
+            if (!recovery_check || recovery_check[j])
+                (C.ref.size() < missing ? C.ref : C.check).push_back(uint32_t(j));
+        const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        locate_degraded_dev(ctx, sw.w, high != 0, g, V, C, s, &H);
+        return set_err(err, RS_OK);
+    });
+}
+
+rs_status rs_heal_device_degraded(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, void *d_orig,
+                                  uint64_t orig_stride, const uint8_t *orig_present, void *d_rec, uint64_t rec_stride,
+                                  const uint8_t *recovery_check, void *d_restored, uint64_t restored_stride,
+                                  uint32_t mode, uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch,
+                                  uint8_t *d_action, void *stream, rs_error *err) {
+    return rs_heal_device_degraded_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, orig_present, d_rec,
+                                         rec_stride, 0, recovery_check, d_restored, restored_stride, 0, mode, max_rows,
+                                         d_located, d_mismatch, d_action, stream, err);
 }
 
 // ---- heal: the locate that also writes the correction (include/rs_mi355x.h) ----

@@ -543,6 +543,32 @@ struct HealArgs : LocateArgs {
 };
 hipError_t launch_heal(const HealArgs &A, hipStream_t stream);
 
+// ---- degraded heal (rs_heal_device_degraded*, rs_locate.hip; DESIGN.md "Degraded heal") ----
+// launch_locate_log_rows is launch_locate_log over a row list: logs[r * pitch + i0 + c]
+// = log of element c of row rows[r] of `coef`, r < nrows -- the table log U[r][q], m x N,
+// from the restored rows (rows: the missing originals) of the unit stripe's repair.
+// launch_heal_degraded runs between the confirm and the rename of a degraded locate's
+// group, after a find with `differ`: located[b] is still an information position q and
+// `want` the completed stripe's encode.  It writes every action[b] and, where action[b]
+// != 0, the stripe: a located q whose shard map[q] is an original (kHealOriginal and the
+// mode bit) or a reference row (kHealRecovery and the mode bit): that shard ^= e = D_j0 /
+// T[j0][q], and row miss[r] of `restored` ^= U[r][q] * e for r < m; kLocateRows (the mode
+// bit, differ[b] <= max_rows): launch_heal's copy over the check rows.  grid = (the
+// confirm's pack tiles, row groups over max(m, nsel), stripes); a located stripe's m
+// restored rows are dealt round the row groups.
+struct HealDegradedArgs : HealArgs {
+    const int32_t *map = nullptr;    // N words (launch_locate_unit_degraded)
+    const uint32_t *miss = nullptr;  // the m missing originals in order
+    const uint16_t *logu = nullptr;  // log U[r][q] at r * N + q, 4-byte aligned
+    uint32_t m = 0;
+    uint8_t *restored = nullptr;
+    uint64_t restored_stride = 0, restored_bstride = 0;
+};
+hipError_t launch_locate_log_rows(const uint8_t *coef, uint64_t stride, const uint32_t *rows, uint32_t nrows,
+                                  uint32_t i0, uint32_t count, uint32_t pitch, const uint16_t *log_table,
+                                  uint16_t *logs, hipStream_t stream);
+hipError_t launch_heal_degraded(const HealDegradedArgs &A, hipStream_t stream);
+
 // ---- robust locate (rs_locate_device_robust*, rs_locate_robust.hip; DESIGN.md "Robust locate") ----
 // After the unfused verify, as the locate's launches, with t <= kRobustMaxOutliers
 // and 2 (t + 1) <= nsel.  launch_locate_find_pairs (grid = stripes x pairs) writes every

@@ -31,6 +31,26 @@
 //   k_coef_unit_degraded   the unit stripe of a slab of information positions
 //   k_locate_rename        a located position that is a missing original: N + the
 //                          reference row that stands in for it
+//
+// and of a degraded heal (rs_heal_device_degraded*, DESIGN.md "Degraded heal"), between
+// the confirm and the rename of a degraded locate, while located[b] is still the
+// information position q and the completed stripe's encode is still in scratch:
+//
+//   k_coef_log_rows        k_coef_log_slab over a row list: the table log U[r][q], m x N,
+//                          from the restored rows of the unit stripe's repair
+//   k_heal_degraded        a located position q: the shard it lives in ^= e (e = D_j0 /
+//                          T[j0][q], the confirm's) and restored row r ^= U[r][q] * e for
+//                          every missing original; a ROWS stripe: k_heal's copy of the
+//                          flagged check rows; one action byte per stripe
+//
+// No ordering hazard inside k_heal_degraded, by construction: e comes from check row
+// K[0] of the caller's recovery matrix and from scratch, and neither is ever written on
+// a located stripe (the located shard is a present original or a reference row, the
+// restored rows are the missing originals'); each pack of the located shard is
+// read-modify-written by exactly one lane (row group 0 of its pack tile), and each pack
+// of a restored row by the one lane of the one row group that owns the row (r mod the
+// number of row groups), from the row itself and e alone.  Where the restored matrix
+// is the originals', its rows were written by the repair earlier on the same stream.
 #include <cstdio>
 
 #include "rs_device.hpp"
@@ -262,6 +282,92 @@ __global__ __launch_bounds__(256) void k_heal(const HealArgs A) {
     }
 }
 
+// k_coef_log_slab over the rows a list names: logs[r * pitch + i0 + c] = log of element
+// c of row rows[r] of `coef`, r < nrows (a degraded heal's table log U: coef is the
+// first output of the unit stripe's repair, rows the missing originals).
+__global__ void k_coef_log_rows(const uint8_t *coef, uint64_t stride, const uint32_t *rows, uint32_t nrows, uint32_t i0,
+                                uint32_t count, uint32_t pitch, const uint16_t *log_table, uint16_t *logs) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (c >= count || r >= nrows) return;
+    const uint8_t *p = coef + uint64_t(rows[r]) * stride + (c >> 5) * 64u + (c & 31u);
+    logs[uint64_t(r) * pitch + i0 + c] = log_table[uint32_t(p[0]) | uint32_t(p[32]) << 8];
+}
+
+// The confirm's x and z; gridDim.y = the row groups of rows_per_group rows over max(m,
+// nsel) rows.  On a ROWS stripe group y has check rows y * rows_per_group ...; on a
+// located stripe the m restored rows are dealt round the groups (row r to group r mod
+// gridDim.y), so that few missing originals under many check rows still spread over m
+// workgroups per pack tile.  The grid is sized for the ROWS case on purpose: on a
+// located stripe only the groups y < m have a row, each of them forms e for itself (one
+// syndrome load of row K[0] and one table fetch), and the others leave after two scalar
+// loads.  located[b] is still an information position.  Every branch
+// but the pack bound is uniform over the workgroup; workgroup (0, 0) of a stripe stores
+// action[b]; a stripe with nothing to heal leaves at once, and so does a row group with
+// no row.
+__global__ __launch_bounds__(256) void k_heal_degraded(const HealDegradedArgs A) {
+    const uint64_t b = blockIdx.z;
+    const int32_t loc = __builtin_amdgcn_readfirstlane(A.located[b]);
+    uint32_t action = 0, shard = 0;
+    if (loc >= 0) {  // the shard position loc lives in: original loc, or N + a reference row
+        shard = __builtin_amdgcn_readfirstlane(const_words(A.map)[loc]);
+        const uint32_t bit = shard < A.N ? kHealOriginal : kHealRecovery;
+        if (A.mode & bit) action = bit;
+    } else if (loc == kLocateRows && (A.mode & kHealRecovery)) {
+        if (uint32_t(__builtin_amdgcn_readfirstlane(A.differ[b])) <= A.max_rows) action = kHealRecovery;
+    }
+    if ((blockIdx.x | blockIdx.y | threadIdx.x) == 0) A.action[b] = uint8_t(action);
+    if (!action) return;
+    const uint32_t r0 = blockIdx.y * A.rows_per_group;
+    const uint32_t r1 = r0 + A.rows_per_group < A.nsel ? r0 + A.rows_per_group : A.nsel;
+    if (loc >= 0 ? blockIdx.y >= A.m : r0 >= A.nsel) return;  // (row group 0 always has a row: m >= 1, nsel >= 2)
+    const uint32_t pk = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = pk < A.packs;
+    const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
+    const uint8_t *want = A.want + b * A.want_bstride;
+    const ConstWords rows = const_words(A.rows);
+    if (loc >= 0) {
+        const ConstWords lut = const_words(A.lut), logu = const_words(A.logu), miss = const_words(A.miss);
+        uint32_t el, eh;  // e = D_j0 / T[j0][loc], once per workgroup
+        locate_error(A, const_words(A.logs), lut, rows[0], uint32_t(loc), want, A.have + b * A.have_bstride, io, ok, el,
+                     eh);
+        if (blockIdx.y == 0 && ok) {
+            uint8_t *p = shard < A.N ? A.orig + b * A.orig_bstride + uint64_t(shard) * A.orig_stride
+                                     : A.rec + b * A.have_bstride + uint64_t(shard - A.N) * A.have_stride;
+            p += io.lo;
+            st_word(p, ld_word(p, io) ^ el, io);
+            st_word(p + io.hi_delta, ld_word(p + io.hi_delta, io) ^ eh, io);
+        }
+        uint8_t *out = A.restored + b * A.restored_bstride;
+        for (uint32_t r = blockIdx.y; r < A.m; r += gridDim.y) {
+            // restored row r ^= U[r][loc] * e (no entry of U is zero; the sentinel would add nothing)
+            const uint32_t lg = coef_log(logu, A.N, r, uint32_t(loc));
+            uint32_t pl = 0, ph = 0;
+            if (lg != kNoLog) {
+                uint32_t t[kTableWords];
+#pragma unroll
+                for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(lg) * kTableWords + w];
+                gf_muladd4(pl, ph, el, eh, t);
+            }
+            if (!ok) continue;
+            uint8_t *p = out + uint64_t(miss[r]) * A.restored_stride + io.lo;
+            st_word(p, ld_word(p, io) ^ pl, io);
+            st_word(p + io.hi_delta, ld_word(p + io.hi_delta, io) ^ ph, io);
+        }
+        return;
+    }
+    // a ROWS stripe within the threshold: k_heal's copy of the flagged check rows
+    const uint8_t *flags = A.flags + b * A.flag_bstride;
+    uint8_t *rec = A.rec + b * A.have_bstride;
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t j = rows[r];
+        if (!__builtin_amdgcn_readfirstlane(uint32_t(flags[j])) || !ok) continue;
+        const uint8_t *w = want + uint64_t(j) * A.want_stride + io.lo;
+        uint8_t *h = rec + uint64_t(j) * A.have_stride + io.lo;
+        st_word(h, ld_word(w, io), io);
+        st_word(h + io.hi_delta, ld_word(w + io.hi_delta, io), io);
+    }
+}
+
 }  // namespace
 
 hipError_t launch_locate_unit(uint8_t *unit, uint64_t stride, uint32_t i0, uint32_t count, hipStream_t s) {
@@ -335,6 +441,37 @@ hipError_t launch_heal(const HealArgs &A0, hipStream_t s) {
     if (grid.y > 65535) return hipErrorInvalidValue;
     k_heal<<<grid, threads, 0, s>>>(A);
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_heal");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_log_rows(const uint8_t *coef, uint64_t stride, const uint32_t *rows, uint32_t nrows,
+                                  uint32_t i0, uint32_t count, uint32_t pitch, const uint16_t *log_table,
+                                  uint16_t *logs, hipStream_t s) {
+    if (!count || !nrows) return hipSuccess;
+    if (!rows || nrows > 65535 || uint64_t(i0) + count > pitch || stride < 64 * ((uint64_t(count) + 31) / 32))
+        return hipErrorInvalidValue;
+    k_coef_log_rows<<<dim3((count + 63) / 64, nrows), 64, 0, s>>>(coef, stride, rows, nrows, i0, count, pitch,
+                                                                   log_table, logs);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_coef_log_rows");
+    return hipGetLastError();
+}
+
+hipError_t launch_heal_degraded(const HealDegradedArgs &A0, hipStream_t s) {
+    if (!A0.stripes) return hipSuccess;
+    if (A0.nsel < 2 || !A0.packs || A0.stripes > 65535 || !A0.rows || !A0.differ || !A0.action || !A0.orig ||
+        !A0.rec || !A0.mode || (A0.mode & ~(kHealOriginal | kHealRecovery)) || !A0.m || A0.m > A0.N || !A0.map ||
+        !A0.miss || !A0.logu || !A0.restored)
+        return hipErrorInvalidValue;
+    HealDegradedArgs A = A0;
+    // the confirm's x and z (launch_locate_confirm); y over the larger of the two row counts
+    const uint32_t threads = A.packs >= 256 ? 256u : (A.packs + 63u) / 64u * 64u, tiles = (A.packs + threads - 1) / threads;
+    const uint32_t nrows = A.m > A.nsel ? A.m : A.nsel;
+    const uint64_t units = uint64_t(nrows) * tiles * A.stripes;
+    A.rows_per_group = uint32_t(units / 1024 < 1 ? 1 : units / 1024 > 16 ? 16 : units / 1024);
+    const dim3 grid(tiles, (nrows + A.rows_per_group - 1) / A.rows_per_group, A.stripes);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    k_heal_degraded<<<grid, threads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_heal_degraded");
     return hipGetLastError();
 }
 

@@ -139,6 +139,10 @@ _sig("rs_heal_device_robust", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp,
      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _E)
 _sig("rs_heal_device_robust_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _E)
+_sig("rs_heal_device_degraded", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, ctypes.c_char_p, _vp, _u64,
+     ctypes.c_char_p, _vp, _u64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
+_sig("rs_heal_device_degraded_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, ctypes.c_char_p, _vp,
+     _u64, _u64, ctypes.c_char_p, _vp, _u64, _u64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_engine_fft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_ifft", _int, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp)
 _sig("rs_engine_mul", _int, _vp, _vp, _u64, ctypes.c_uint16, _vp)
@@ -1487,6 +1491,97 @@ def heal_device_batch(original_count: int, recovery_count: int, shard_bytes: int
                                      d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows, mode,
                                      max_rows, _ptr(d_located), _ptr(d_mismatch), _ptr(d_action), _stream(stream),
                                      ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_action
+
+
+def _heal_degraded_args(original_present, original_count, recovery_rows, recovery_count, mode, max_rows):
+    """The heal's mode and threshold, then the degraded masks with the heal's three check rows
+    (the library's order)."""
+    mode, max_rows = int(mode), int(max_rows)
+    if mode == 0 or mode & ~(HEAL_ORIGINAL | HEAL_RECOVERY):
+        raise ValueError(f"mode: HEAL_ORIGINAL | HEAL_RECOVERY, at least one (locate_device_degraded takes none), "
+                         f"got {mode}")
+    if not 0 <= max_rows < 1 << 32:
+        raise ValueError(f"max_rows: 0 .. 2^32 - 1, got {max_rows}")
+    present = _check_mask(present_mask(original_present), original_count, "original_present")
+    rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
+                                                          "recovery_rows")
+    m = sum(1 for b in present if not b)
+    c = recovery_count if rows is None else sum(1 for b in rows if b)
+    if m <= c < m + 3:  # (c < m: the library's NotEnoughShards, with its counts)
+        raise ValueError(f"recovery_rows: {m} missing originals take {m} of the {c} selected recovery rows as "
+                         f"reference rows; a heal writes on the evidence of three more at least")
+    return present, rows, mode, max_rows
+
+
+def heal_device_degraded(original_count: int, recovery_count: int, shard_bytes: int, d_original, original_present,
+                         d_recovery, d_restored, recovery_rows=None, mode: int = HEAL_ORIGINAL | HEAL_RECOVERY,
+                         max_rows: int = 0, d_located=None, d_mismatch=None, d_action=None, stream=None,
+                         rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """locate_device_degraded that also writes the correction, in place (rs_heal_device_degraded).
+    A located present original i (mode & HEAL_ORIGINAL) or reference row j (located =
+    original_count + j, mode & HEAL_RECOVERY) becomes shard ^ e, and every missing original's row
+    of d_restored (required; may be d_original) the clean original.  mode & HEAL_RECOVERY: the
+    differing check rows of a LOCATE_ROWS stripe become the encode of the completed stripe, when
+    at most max_rows differ -- which does NOT prove the information shards intact (the caveat in
+    include/rs_mi355x.h).  Returns (located, mismatch, action): the degraded locate's report of
+    the stripe as found, and a uint8 tensor [1] holding HEAL_ORIGINAL, HEAL_RECOVERY or 0 (the
+    stripe is as locate_device_degraded leaves it).  Needs m + 3 selected rows.  Asynchronous on
+    `stream`."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    present, rows, mode, max_rows = _heal_degraded_args(original_present, original_count, recovery_rows,
+                                                        recovery_count, mode, max_rows)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original")
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
+    if d_restored is None:
+        raise ValueError("d_restored: a degraded heal needs it (it may be d_original)")
+    _check_matrix(d_restored, original_count, shard_bytes, "d_restored")
+    d_located = _check_located(d_located, (1,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    d_action = _check_action(d_action, (1,), d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_heal_device_degraded(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
+                                        _ptr(d_original), _row_stride(d_original), present, _ptr(d_recovery),
+                                        _row_stride(d_recovery), rows, _ptr(d_restored), _row_stride(d_restored),
+                                        mode, max_rows, _ptr(d_located), _ptr(d_mismatch), _ptr(d_action),
+                                        _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_action
+
+
+def heal_device_degraded_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original,
+                               original_present, d_recovery, d_restored, recovery_rows=None,
+                               mode: int = HEAL_ORIGINAL | HEAL_RECOVERY, max_rows: int = 0, d_located=None,
+                               d_mismatch=None, d_action=None, stream=None, rate_: int = RATE_DEFAULT,
+                               ctx: Optional[Context] = None):
+    """heal_device_degraded on a batch of stripes sharing ONE presence mask and ONE row mask
+    (rs_heal_device_degraded_batch); tensors [stripes, rows, shard_bytes].  Returns (located
+    [stripes], mismatch [stripes, recovery_count], action [stripes])."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    present, rows, mode, max_rows = _heal_degraded_args(original_present, original_count, recovery_rows,
+                                                        recovery_count, mode, max_rows)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    if d_restored is None:
+        raise ValueError("d_restored: a degraded heal needs it (it may be d_original)")
+    _check_matrix(d_restored, original_count, shard_bytes, "d_restored", 3)
+    if d_restored.shape[0] != n:
+        raise ValueError("original and restored batches differ in stripe count")
+    x_row, x_b = _batch_strides(d_restored)
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_action = _check_action(d_action, (n,), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_heal_device_degraded_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                              d_original.data_ptr(), o_row, o_b, present, d_recovery.data_ptr(),
+                                              r_row, r_b, rows, d_restored.data_ptr(), x_row, x_b, mode, max_rows,
+                                              _ptr(d_located), _ptr(d_mismatch), _ptr(d_action), _stream(stream),
+                                              ctypes.byref(err)), err)
     return d_located, d_mismatch, d_action
 
 
