@@ -1396,9 +1396,17 @@ rs_status rs_check_device(rs_context *ctx);
  * 2048 runs single-chunk 2-element encodes of 2^10 rows as the 4-element
  * kernel of 2^9 pair rows (the quad encode; off by default: bit-exact but
  * slower; RS_MI355X_QUAD=1 at context creation: on), adding 4096 turns it off.
+ * Single-chunk encodes of N = M = 2^7 .. 2^11 shards of whole 64-byte blocks,
+ * 4-byte aligned, every recovery row asked for, run the column kernel's dense
+ * entry, which takes the row maps' geometry as decided by the host instead of
+ * testing it per lane (on by default; RS_MI355X_DENSE=0 at context creation:
+ * never): adding 8192 turns it on, adding 16384 off (the general entry).
  * Neither bit of a pair: the context's defaults (its environment included).
  * A/B and tests; results are identical in every mode. */
 rs_status rs_mono_enable(rs_context *ctx, int enable);
+/* Launches of the dense entry by this process so far (tests, A/B: the profile
+ * records name the general and the dense entry alike, k_mono<...>). */
+uint64_t rs_mono_dense_launches(void);
 
 /* ---- GF(2^16) tables (src/engine/tables.rs), host copies ---- */
 const uint16_t *rs_table_exp(void);       /* 65536 */

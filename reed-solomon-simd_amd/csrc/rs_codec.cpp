@@ -386,6 +386,10 @@ struct rs_context {
     // encodes of 2^10 rows as the 4-element kernel of 2^9 pair rows (RS_MI355X_QUAD=0/1;
     // rs_mono_enable + 2048: on, + 4096: off)
     bool quad = false, quad_default = false;
+    // dense entry of the staged single-chunk encode (rs_mono.hip k_mono_dense) where
+    // rs_mono_dense.hpp mono_dense_ok holds: N = M = 2^L, shards of whole blocks, aligned
+    // (RS_MI355X_DENSE=0/1; rs_mono_enable + 8192: on, + 16384: off)
+    bool dense = true, dense_default = true;
     // multi-chunk encodes of 2^2..2^7-row transforms on k_chunks (use_chunks below;
     // RS_MI355X_CHUNKS=0/1; rs_mono_enable + 512: on, + 1024: off)
     bool chunks = true, chunks_default = true;
@@ -1054,7 +1058,7 @@ void encode_high(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint
         Mo.fft_img = 0;
         const uint64_t bytes = (N + out_hi - out_lo) * uint64_t(g.packs) * 8 * g.stripes;
         if (!try_quad(ctx, L, C, Mo, s, bytes) && !try_lane(ctx, L, C, Mo, s, bytes))
-            launch_mono(rs::kMonoEncodeHigh, L, Mo, s, bytes);
+            launch_mono(rs::kMonoEncodeHigh | (ctx->dense ? 0 : rs::kMonoNoDense), L, Mo, s, bytes);
         return;
     }
     if (use_chunks(ctx, L, g, C, true)) {
@@ -1151,7 +1155,7 @@ void encode_low(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint6
         Mo.fft_img_step = 1;
         const uint64_t bytes = (N + out_hi - out_lo) * uint64_t(g.packs) * 8 * g.stripes;
         if (!try_quad(ctx, L, C, Mo, s, bytes) && !try_lane(ctx, L, C, Mo, s, bytes))
-            launch_mono(rs::kMonoEncodeLow, L, Mo, s, bytes);
+            launch_mono(rs::kMonoEncodeLow | (ctx->dense ? 0 : rs::kMonoNoDense), L, Mo, s, bytes);
         return;
     }
     if (use_chunks(ctx, L, g, C, false)) {
@@ -2667,6 +2671,8 @@ rs_status rs_context_create(int device, rs_context **out) {
         if (const char *ud = getenv("RS_MI355X_UPDATE_DIRECT_MAX")) ctx->update_direct_max = uint32_t(strtoul(ud, nullptr, 10));
         if (const char *vf = getenv("RS_MI355X_VERIFY_FUSED")) ctx->verify_fused = atoi(vf) != 0;
         ctx->quad_default = ctx->quad;
+        if (const char *de = getenv("RS_MI355X_DENSE")) ctx->dense = de[0] == '1';
+        ctx->dense_default = ctx->dense;
         if (const char *ck = getenv("RS_MI355X_CHUNKS")) {  // 0 off, 1 default routing, 2 every supported shape
             ctx->chunks = ck[0] != '0';
             ctx->chunks_forced = ck[0] == '2';
@@ -4340,12 +4346,16 @@ rs_status rs_mono_enable(rs_context *ctx, int enable) {
     ctx->half = (enable & 128) ? true : (enable & 256) ? false : ctx->half_default;
     // + 2048: quad encode on, + 4096: off
     ctx->quad = (enable & 2048) ? true : (enable & 4096) ? false : ctx->quad_default;
+    // + 8192: dense encode entry on, + 16384: off
+    ctx->dense = (enable & 8192) ? true : (enable & 16384) ? false : ctx->dense_default;
     // + 512: multi-chunk kernel on, + 1024: off
     ctx->chunks = (enable & 512) ? true : (enable & 1024) ? false : ctx->chunks_default;
     // (neither bit: the context's defaults, RS_MI355X_CHUNKS=2's forced routing included)
     ctx->chunks_forced = (enable & 512) ? true : (enable & 1024) ? false : ctx->chunks_forced_default;
     return RS_OK;
 }
+
+uint64_t rs_mono_dense_launches(void) { return rs::mono_dense_launches(); }
 
 rs_status rs_check_device(rs_context *ctx) {
     if (!ctx) return RS_ERR_INVALID_ARGUMENT;

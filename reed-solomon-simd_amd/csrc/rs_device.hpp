@@ -302,6 +302,28 @@ struct MonoLead {
     uint32_t imgs;  // ifft_img | fft_img << 16
 };
 static_assert(sizeof(MonoLead) == 56, "14 dwords, no padding");
+// The dense form of that entry (rs_mono.hip k_mono_dense; rs_mono_dense.hpp
+// mono_dense_ok decides on the host): every transform row [0, 2^L) is a row of the
+// one source map and of the destination map, in full, 4-byte aligned packs.  The row
+// ranges and the shard format say nothing then, and their four dwords carry the
+// destination map instead: a single-stripe launch reads no argument from memory.
+struct MonoLeadDense {
+    const uint8_t *src;
+    uint64_t src_stride;  // (both strides < 2^24, 2^L rows of them <= 2^32 bytes: mono_dense_ok)
+    uint8_t *dst;
+    uint64_t dst_stride;
+    uint32_t packs, packs_per_xcd;
+    const uint32_t *img;
+    uint32_t img_words;
+    uint32_t imgs;  // ifft_img | fft_img << 16
+};
+static_assert(sizeof(MonoLeadDense) == 56, "14 dwords, no padding");
+// launch_mono's mode + kMonoNoDense: the general entry also where the dense one could run
+// (rs_mono_enable + 8192, RS_MI355X_DENSE=0)
+constexpr int kMonoNoDense = 0x100;
+// launches of the dense entry by this process so far (tests, A/B: the profile records
+// name both forms k_mono<...>, as the traces of the general entry always have)
+uint64_t mono_dense_launches();
 struct MonoArgs : MonoCore {
     // fused-eval_poly decode: erased / received bits of the 2^L work rows, as in EvalArgs
     uint32_t erased[kMonoFusedRows / 32] = {}, received[kMonoFusedRows / 32] = {};

@@ -28,6 +28,7 @@
 
 #include "rs_device.hpp"
 #include "rs_gf.hpp"
+#include "rs_mono_dense.hpp"
 #include "rs_stage_map.hpp"
 
 namespace rs {
@@ -821,6 +822,22 @@ constexpr uint32_t paired_delta(int j) {
     return (uint32_t(j & 1) << S::v.maps[I].lane[0]) + reg_rows<S, I, LR>(j >> 1);
 }
 
+// Dense rows (k_mono_dense; rs_mono_dense.hpp mono_dense_ok holds): every row of the
+// transform is a row of the map, packs are full and 4-byte aligned.  The address of
+// word j is a wave-uniform base (the stripe's base, the wave's row bits, the pack's
+// offset and the compile-time row delta of j: scalar arithmetic) plus one 32-bit lane
+// offset (the lane's row bits times the stride, + 32 for the high word's lanes) that
+// all of a lane's loads or stores share -- no range test, no stand-in row, no 64-bit
+// lane arithmetic.  Bound (mono_dense_stride_ok): stride < 2^24, 2^L * stride <= 2^32.
+template <typename S, int I, int LR>
+__device__ __forceinline__ uint32_t dense_lane_off(uint32_t lane, uint32_t stride) {
+    return __umul24(paired_row<S, I, LR>(lane, 0, 0), stride) + ((lane & 1u) << 5);
+}
+template <typename S, int I, typename P>
+__device__ __forceinline__ P *dense_base(P *base, uint32_t wave, uint32_t stride, uint32_t lo) {
+    return base + (uint64_t(lane_rows<S, I>(0, wave) * stride) + lo);
+}
+
 // Load transform rows `chunk * n + row` (placement: start of the IFFT) as
 // paired words; finish_col completes them.  Missing rows inside the caller's
 // matrices are read and discarded by the decode's scaling.  okm bit j: word j
@@ -830,11 +847,26 @@ constexpr uint32_t paired_delta(int j) {
 // (2-element packs: the paired words are the 16-bit low and high halves)
 // (AT_FFT: rows in the placement at the start of the FFT -- the end of the IFFT --
 // instead: the half-split kernels' work rows, kMonoHalfF)
-template <int L, int LR, int SPLIT = 0, int E = 4, int BYTES = -1, bool AT_FFT = false>
+// (DENSE, k_mono_dense: see dense_lane_off)
+template <int L, int LR, int SPLIT = 0, int E = 4, int BYTES = -1, bool AT_FFT = false, bool DENSE = false>
 __device__ __forceinline__ void issue_col(const MonoCore &A, uint32_t chunk, const PackIO &io, const StripeBases &sb,
                                           uint32_t (&w)[2 << LR], uint32_t &okm, uint32_t lane, uint32_t wave,
                                           bool live = true) {
     using S = SeqOf<L, LR, AT_FFT, SPLIT>;
+    if constexpr (DENSE) {
+        static_assert(!AT_FFT && BYTES < 0, "dense rows: the single-chunk encode's loads");
+        // 2-element packs: the aligned dword around the half, as below (finish_col picks
+        // it out by io.lo & 2, which no lane and no row changes: rows are 4-byte aligned)
+        const uint32_t st = uint32_t(A.src[0].stride);
+        const uint32_t voff = dense_lane_off<S, 0, LR>(lane, st);
+        const uint8_t *const ub = dense_base<S, 0>(sb.src0, wave, st, E == 2 ? io.lo & ~3u : io.lo);
+        static_for<0, (2 << LR)>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            w[j] = *reinterpret_cast<const uint32_t *>(ub + uint64_t(paired_delta<S, 0, LR>(j) * st) + voff);
+        });
+        okm = ~0u;  // (a constant: finish_col's selects fold away)
+        return;
+    }
     const uint32_t base = chunk * (1u << L);
     const uint32_t off = io.lo + ((lane & 1u) ? io.hi_delta : 0u);
     // a row every lane may read (the first source row): lanes without a row of
@@ -1103,8 +1135,9 @@ __device__ __forceinline__ void verify_issue(const MonoCore &A, const PackIO &io
 // (VERIFY: nothing is stored to A.dst -- the caller's word at the address of each
 // store, loaded by verify_issue, is compared with the finished word, and a
 // difference sets the row's flag, vp)
+// (DENSE, k_mono_dense: see dense_lane_off)
 template <int L, int LR, bool REVEAL, int SPLIT = 0, int E = 4, bool AT_IFFT = false, bool TWO = false,
-          bool VERIFY = false>
+          bool VERIFY = false, bool DENSE = false>
 __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *rowinfo, uint32_t chunk,
                                           const PackIO &io, const StripeBases &sb, Col<L, LR, E> &c, uint32_t lane,
                                           uint32_t wave, const RevealTabs<LR> *rt = nullptr,
@@ -1151,6 +1184,23 @@ __device__ __forceinline__ void store_col(const MonoCore &A, const uint32_t *row
         }
         xpose<0>(w[2 * i], w[2 * i + 1], lane);
     });
+    if constexpr (DENSE) {
+        static_assert(!REVEAL && !AT_IFFT && !TWO && !VERIFY, "dense rows: the single-chunk encode's stores");
+        const uint32_t st = uint32_t(A.dst.stride);
+        const uint32_t voff = dense_lane_off<S, I, LR>(lane, st);
+        uint8_t *const ub = dense_base<S, I>(sb.dst, wave, st, io.lo);
+        static_for<0, 2 * R>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            uint8_t *p = ub + uint64_t(paired_delta<S, I, LR>(j) * st) + voff;
+            if constexpr (E == 2) *reinterpret_cast<uint16_t *>(p) = uint16_t(w[j]);
+#ifndef RS_MONO_NO_NT_STORE
+            else __builtin_nontemporal_store(w[j], reinterpret_cast<uint32_t *>(p));
+#else
+            else *reinterpret_cast<uint32_t *>(p) = w[j];
+#endif
+        });
+        return;
+    }
     const uint32_t off = io.lo + ((lane & 1u) ? io.hi_delta : 0u);
     const uint32_t r0 = paired_row<S, I, LR>(lane, wave, 0) + base;
     uint8_t *const p0 = const_cast<uint8_t *>(map_base(A.dst, sb.dst, r0));  // (see row_at)
@@ -1991,9 +2041,15 @@ using MonoArgM = std::conditional_t<MASKS, MonoMaskArgs, MonoArgT<MODE, STAGED>>
 // Everything the prologue's row and table loads need is in the first group; the
 // destination map, the only other thing an encode reads, is waited for after
 // those loads are issued (pin_rest).
+// DENSE (k_mono_dense, a form of PRE): the host has found every transform row in both
+// maps, in full aligned packs (rs_mono_dense.hpp); `dense` carries both maps' bases and
+// strides in SGPRs, the rows are addressed without range tests (dense_lane_off), and
+// nothing is left for pin_rest to wait for.
 template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, bool MASKS = false, bool TWO = false,
-          bool VERIFY = false, bool PRE = false, typename KA = MonoArgM<MODE, STAGED, MASKS>>
-__device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const MonoLead *lead = nullptr) {
+          bool VERIFY = false, bool PRE = false, bool DENSE = false, typename KA = MonoArgM<MODE, STAGED, MASKS>>
+__device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const MonoLead *lead = nullptr,
+                                          [[maybe_unused]] const MonoLeadDense *dense = nullptr) {
+    static_assert(!DENSE || PRE, "dense rows: a form of the preloaded encode entry");
     static_assert(!PRE || (STAGED && !SPLIT && !MASKS && !TWO && !VERIFY &&
                            (MODE == kMonoEncodeHigh || MODE == kMonoEncodeLow)),
                   "preloaded arguments: the staged single-chunk encode");
@@ -2006,7 +2062,19 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
     MonoCore A;  // the scalar arguments; the erasure bitmaps stay in K
     uint32_t ew[4] = {0, 0, 0, 0}, rw[4] = {0, 0, 0, 0};  // staged decode: the wave's bitmap words
     uint32_t skip_stripe = 0;  // MASKS: the stripe's descriptor says skip
-    if constexpr (PRE) {  // (nothing to wait for here: see pin_rest)
+    if constexpr (DENSE) {  // (k_mono_dense: both maps arrived in SGPRs, every row [0, 2^L) is theirs)
+        A.packs = dense->packs;
+        A.packs_per_xcd = dense->packs_per_xcd;
+        A.nsrc = 1;
+        A.src[0] = RowMap{dense->src, dense->src_stride, 0u, 1u << L};
+        A.src[1] = A.src[0];
+        A.dst = RowMap{dense->dst, dense->dst_stride, 0u, 1u << L};
+        A.img = dense->img;
+        A.img_words = dense->img_words;
+        A.ifft_img = dense->imgs & 0xFFFFu;
+        A.fft_img = dense->imgs >> 16;
+        A.fmt = ShardFormat{};
+    } else if constexpr (PRE) {  // (nothing to wait for here: see pin_rest)
         A.packs = lead->packs;
         A.packs_per_xcd = lead->packs_per_xcd;
         A.nsrc = 1;
@@ -2130,7 +2198,10 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
                                                                              const_cast<uint8_t *>(A.dst.base)};
     // the pack's bytes in the caller's rows (tails: shards.rs:38-74)
     // (quad encode: 2-element column packs, computed as 4-element pair-row packs)
-    const PackIO io = E == 4 && MODE != kMonoQuadEnc ? pack_io(A.fmt, pk) : pack_io2(A.fmt, pk);
+    // (dense rows: full packs, aligned -- pack_io / pack_io2's first form)
+    const PackIO io = DENSE ? (E == 4 ? PackIO{(pk >> 3) * 64u + (pk & 7u) * 4u, 32u, 4u, false}
+                                      : PackIO{(pk >> 4) * 64u + (pk & 15u) * 2u, 32u, 2u, false})
+                      : E == 4 && MODE != kMonoQuadEnc ? pack_io(A.fmt, pk) : pack_io2(A.fmt, pk);
     Dst2 d2;
     if constexpr (TWO) {
         d2.m = K.dst2;
@@ -2270,7 +2341,8 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
             uint32_t w[2 << LR] = {};
             uint32_t okm = 0;
             auto issue_rows = [&](auto bytes) {
-                issue_col<L, LR, PK, E, decltype(bytes)::value>(A, HALF_I ? hh : 0u, io, sb, w, okm, lane, wave, live);
+                issue_col<L, LR, PK, E, decltype(bytes)::value, false, DENSE>(A, HALF_I ? hh : 0u, io, sb, w, okm, lane,
+                                                                              wave, live);
             };
             // kMonoHalfF: the two halves' IFFT rows (work rows, placement at the FFT's start)
             uint32_t w2[2 << LR] = {};
@@ -2402,7 +2474,7 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
                 if constexpr (kDma && G::B0) issue_v1();  // behind every DMA of the prologue
                 issue_quad_tabs();
                 if constexpr (VERIFY) verify_issue<L, LR, PK, E>(A, io, sb, vp, lane, wave);
-                if constexpr (PRE) {
+                if constexpr (PRE && !DENSE) {
                     // pin_rest: the destination map comes from the argument segment (the
                     // other arguments an encode reads arrived in SGPRs).  Its scalar loads
                     // are waited for here, behind the row and table loads, and the values
@@ -2719,8 +2791,8 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
                 quad_layer0<L, LR, SQ, SQ::v.count, true>(c, qtab + QW * kQuad0Slot, lane, wave);  // FFT layer 0
                 store_quad<L, LR, PK>(A, io, sb, c, lane, wave);
             } else {
-                store_col<L, LR, DEC || HFD, PK, E, false, TWO, VERIFY>(A, ri, HALF_F ? hh : 0u, io, sb, c, lane, wave,
-                                                                        kPreReveal && G::WB > 0 ? &rt : nullptr, d2, &vp);
+                store_col<L, LR, DEC || HFD, PK, E, false, TWO, VERIFY, DENSE>(
+                    A, ri, HALF_F ? hh : 0u, io, sb, c, lane, wave, kPreReveal && G::WB > 0 ? &rt : nullptr, d2, &vp);
             }
             RS_MSTAMP(11);
       };
@@ -2797,6 +2869,23 @@ k_mono(const uint8_t *src, uint64_t src_stride, uint32_t src_begin, uint32_t src
                         imgs};
     mono_body<L, LR, MODE, STAGED, BATCH, SPLIT, E, false, false, false, true>(R, &lead);
 }
+// The dense form of that entry (rs_device.hpp MonoLeadDense): the launch's rows are
+// all of [0, 2^L) in both maps, in full aligned packs (rs_mono_dense.hpp mono_dense_ok,
+// tested by launch_ls).  The row ranges and the shard format are not passed; the
+// destination map takes their SGPRs, so nothing of R is read but a batch's stripe
+// strides.  Row addressing: dense_lane_off.
+template <int L, int LR, int MODE, bool BATCH, int E>
+__global__ void __launch_bounds__(1 << (L - LR))
+k_mono_dense(const uint8_t *src, uint64_t src_stride, uint8_t *dst, uint64_t dst_stride, uint32_t packs,
+             uint32_t packs_per_xcd, const uint32_t *img, uint32_t img_words, uint32_t imgs, const MonoCore R) {
+    const MonoLeadDense lead{src, src_stride, dst, dst_stride, packs, packs_per_xcd, img, img_words, imgs};
+    mono_body<L, LR, MODE, true, BATCH, false, E, false, false, false, true, true>(R, nullptr, &lead);
+}
+// RS_MONO_DENSE 0 (A/B builds): no dense instantiations
+#ifndef RS_MONO_DENSE
+#define RS_MONO_DENSE 1
+#endif
+std::atomic<uint64_t> g_dense_launches{0};
 #ifndef RS_MONO_LR10
 #define RS_MONO_LR10 1
 #endif
@@ -2815,7 +2904,7 @@ constexpr int mono_lr(int L, bool staged) {
 }
 
 template <int L, int MODE, bool STAGED, bool BATCH = false, bool SPLIT = false, int E = 4>
-hipError_t launch_ls(const MonoArgs &A, hipStream_t s) {
+hipError_t launch_ls(const MonoArgs &A, hipStream_t s, [[maybe_unused]] bool dense = false) {
     constexpr int LR = mono_lr(L, STAGED);
     using G = Stage<L, LR, mono_pk(MODE, STAGED, SPLIT), E>;
     size_t lds = STAGED ? size_t(SPLIT ? G::words_split : MODE == kMonoDecode ? G::words_dec : G::words_enc2) * 4
@@ -2829,6 +2918,27 @@ hipError_t launch_ls(const MonoArgs &A, hipStream_t s) {
         if (A.nsrc != 1 || A.img_words > 0xFFFFFFFFull || A.fmt.tail_h > 0xFFFFu || A.ifft_img > 0xFFFFu ||
             A.fft_img > 0xFFFFu)
             return hipErrorInvalidValue;
+        if constexpr (RS_MONO_DENSE != 0) {
+            const DenseRows dsrc{A.src[0].base, A.src[0].stride, A.src[0].row_begin, A.src[0].row_end};
+            const DenseRows ddst{A.dst.base, A.dst.stride, A.dst.row_begin, A.dst.row_end};
+            if (dense && mono_dense_ok(L, A.nsrc, dsrc, ddst, A.fmt.full_packs, A.fmt.tail_h, A.fmt.io_bytes,
+                                       BATCH ? A.src_bstride[0] : 0, BATCH ? A.dst_bstride : 0)) {
+                static std::atomic<uint64_t> attr_dense{0};
+                const auto fd = &k_mono_dense<L, LR, MODE, BATCH, E>;
+                if (lds > 65536) {
+                    hipError_t e = lds_attr_once(attr_dense, reinterpret_cast<const void *>(fd), int(lds));
+                    if (e != hipSuccess) return e;
+                }
+                fd<<<dim3(grid, BATCH ? A.stripes : 1), 1 << (L - LR), lds, s>>>(
+                    A.src[0].base, A.src[0].stride, const_cast<uint8_t *>(A.dst.base), A.dst.stride, A.packs, A.packs_per_xcd,
+                    A.img, uint32_t(A.img_words), A.ifft_img | A.fft_img << 16, static_cast<const MonoCore &>(A));
+                g_dense_launches.fetch_add(1, std::memory_order_relaxed);
+                // (the records' name of the route stays the entry's: the dense form is counted)
+                snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono<%d, %d, %d, true, %s, false, %d>", L, LR, MODE,
+                         BATCH ? "true" : "false", E);
+                return hipGetLastError();
+            }
+        }
         using Fn = void (*)(const uint8_t *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
                             const uint32_t *, uint32_t, uint32_t, const MonoCore);
         const Fn fn = &k_mono<L, LR, MODE, STAGED, BATCH, SPLIT, E>;
@@ -2855,26 +2965,26 @@ hipError_t launch_ls(const MonoArgs &A, hipStream_t s) {
 }
 
 template <int L, int MODE, int E>
-hipError_t launch_staged(const MonoArgs &A, hipStream_t s) {
+hipError_t launch_staged(const MonoArgs &A, hipStream_t s, bool dense) {
     if constexpr (MODE == kMonoDecode && split_l(L)) {
         if (A.split) {
             if (A.stripes > 1) return launch_ls<L, MODE, true, true, true, E>(A, s);
             return launch_ls<L, MODE, true, false, true, E>(A, s);
         }
     }
-    if (A.stripes > 1) return launch_ls<L, MODE, true, true, false, E>(A, s);
-    return launch_ls<L, MODE, true, false, false, E>(A, s);
+    if (A.stripes > 1) return launch_ls<L, MODE, true, true, false, E>(A, s, dense);
+    return launch_ls<L, MODE, true, false, false, E>(A, s, dense);
 }
 
 // Staged (LDS tables) variant: single-chunk transforms, 2 rows per lane.
 template <int L, int MODE>
-hipError_t launch_l(const MonoArgs &A, hipStream_t s) {
+hipError_t launch_l(const MonoArgs &A, hipStream_t s, bool dense) {
     // the staged decode evaluates eval_poly itself; the unstaged one reads rowinfo
     if constexpr (staged_l(L)) {
         if (A.chunks == 1) {  // = mono_staged()
             if (MODE == kMonoDecode && !A.fused_eval) return hipErrorInvalidValue;
-            if (A.elems == 2) return launch_staged<L, MODE, 2>(A, s);
-            return launch_staged<L, MODE, 4>(A, s);
+            if (A.elems == 2) return launch_staged<L, MODE, 2>(A, s, dense);
+            return launch_staged<L, MODE, 4>(A, s, dense);
         }
     }
     if (A.fused_eval || A.stripes > 1 || A.elems != 4) return hipErrorInvalidValue;
@@ -2895,15 +3005,15 @@ hipError_t launch_l(const MonoArgs &A, hipStream_t s) {
 #endif
 
 template <int MODE>
-hipError_t launch_m(int L, const MonoArgs &A, hipStream_t s) {
+hipError_t launch_m(int L, const MonoArgs &A, hipStream_t s, bool dense) {
     if constexpr (!RS_MONO_HAS_MODE(MODE)) return hipErrorNotSupported;
     switch (L) {
-        case 7: if constexpr (RS_MONO_HAS_L(7)) return launch_l<7, MODE>(A, s); break;
-        case 8: if constexpr (RS_MONO_HAS_L(8)) return launch_l<8, MODE>(A, s); break;
-        case 9: if constexpr (RS_MONO_HAS_L(9)) return launch_l<9, MODE>(A, s); break;
-        case 10: if constexpr (RS_MONO_HAS_L(10)) return launch_l<10, MODE>(A, s); break;
-        case 11: if constexpr (RS_MONO_HAS_L(11)) return launch_l<11, MODE>(A, s); break;
-        case 12: if constexpr (RS_MONO_HAS_L(12)) return launch_l<12, MODE>(A, s); break;
+        case 7: if constexpr (RS_MONO_HAS_L(7)) return launch_l<7, MODE>(A, s, dense); break;
+        case 8: if constexpr (RS_MONO_HAS_L(8)) return launch_l<8, MODE>(A, s, dense); break;
+        case 9: if constexpr (RS_MONO_HAS_L(9)) return launch_l<9, MODE>(A, s, dense); break;
+        case 10: if constexpr (RS_MONO_HAS_L(10)) return launch_l<10, MODE>(A, s, dense); break;
+        case 11: if constexpr (RS_MONO_HAS_L(11)) return launch_l<11, MODE>(A, s, dense); break;
+        case 12: if constexpr (RS_MONO_HAS_L(12)) return launch_l<12, MODE>(A, s, dense); break;
         default: break;
     }
     return hipErrorNotSupported;
@@ -3233,12 +3343,15 @@ bool mono_staged(int L, uint32_t chunks) { return L >= 7 && staged_l(L) && chunk
 bool mono_split(int L) { return split_l(L) && staged_l(L); }
 int mono_rows_log2_per_lane(int L, uint32_t chunks) { return mono_lr(L, mono_staged(L, chunks)); }
 
+uint64_t mono_dense_launches() { return g_dense_launches.load(std::memory_order_relaxed); }
+
 hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t s) {
     if (A.packs == 0) return hipSuccess;
-    switch (mode) {
-        case kMonoEncodeHigh: return launch_m<kMonoEncodeHigh>(L, A, s);
-        case kMonoEncodeLow: return launch_m<kMonoEncodeLow>(L, A, s);
-        case kMonoDecode: return launch_m<kMonoDecode>(L, A, s);
+    const bool dense = !(mode & kMonoNoDense);
+    switch (mode & ~kMonoNoDense) {
+        case kMonoEncodeHigh: return launch_m<kMonoEncodeHigh>(L, A, s, dense);
+        case kMonoEncodeLow: return launch_m<kMonoEncodeLow>(L, A, s, dense);
+        case kMonoDecode: return launch_m<kMonoDecode>(L, A, s, dense);
         default: return hipErrorNotSupported;
     }
 }

@@ -160,6 +160,10 @@ int main(int argc, char **argv) {
             A.fft_img_step = 1;
         }
     }
+#ifdef RS_MONO_DENSE  // RS_MONO_PROBE_DENSE=0 in the environment: the general encode entry (A/B)
+    if (const char *de = getenv("RS_MONO_PROBE_DENSE"))
+        if (de[0] == '0' && !dec && !halves) mode |= rs::kMonoNoDense;
+#endif
     const int iters = 1000;
     auto go = [&] { CK(halves ? rs::launch_mono_half(mode, halves, A, 0) : rs::launch_mono(mode, int(L), A, 0)); };
     for (int i = 0; i < 20; ++i) go();
@@ -180,6 +184,9 @@ int main(int argc, char **argv) {
     }
     printf("mono %s%s%s n=%u S=%u: %.2f us/launch (back-to-back), output hash %016llx\n", dec ? "decode" : "encode",
            A.split ? " split" : "", e2 ? " e2" : "", n, S, ms * 1000 / iters, (unsigned long long)hsh);
+#ifdef RS_MONO_DENSE
+    printf("dense entry launches: %llu\n", (unsigned long long)rs::mono_dense_launches());
+#endif
     {  // floor: an empty kernel with the same grid, block and LDS
         const size_t lds = size_t(rs::Stage<10, 1>::words_dec) * 4;
         CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_empty_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
