@@ -491,7 +491,8 @@ rs_status rs_update_set_direct_max(rs_context *ctx, uint32_t k);
  *   Strides (0 = shard_bytes / count rows), alignment and the byte-wise path for
  * unaligned bases or strides as in the _strided / _batch calls.
  * rs_verify_device_batch applies ONE mask to every stripe, as
- * rs_update_device_batch does.  Asynchronous on `stream`, scratch per (context,
+ * rs_update_device_batch does (a mask per stripe:
+ * rs_verify_device_batch_masks below).  Asynchronous on `stream`, scratch per (context,
  * stream).
  *   Errors, all before any device work, in this order: null context, d_original,
  * d_recovery or d_mismatch -> RS_ERR_INVALID_ARGUMENT; rs_validate; the two row
@@ -544,6 +545,79 @@ rs_status rs_verify_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  uint64_t recovery_stride, uint64_t recovery_stripe_stride,
                                  const uint8_t *recovery_check, uint8_t *d_mismatch, void *stream, rs_error *err);
 rs_status rs_verify_set_fused(rs_context *ctx, int mode);
+
+/* ---- verify with a mask per stripe ----
+ * rs_verify_device_batch with recovery_check a HOST array of stripes x
+ * recovery_count bytes of 0/1, stripe-major, NOT NULL: row b of it is stripe b's
+ * mask.  A scrub runs over many objects and each has lost a different set of
+ * recovery rows; this is the batch form that neither reads rows that do not exist
+ * nor falls back to one launch per stripe.  Matrices, strides, alignment, the
+ * byte-wise path, the block and tail layout and d_mismatch (stripes x
+ * recovery_count, dense) are those of rs_verify_device_batch.
+ *   Result: stripe b ends exactly as if rs_verify_device had been called on it with
+ * row b of the mask.  Every byte of d_mismatch is defined after the call.  A row
+ * that stripe b's mask does not select is never read in that stripe -- no prefetch,
+ * no load whose result is discarded -- and its memory need not exist beyond the
+ * address arithmetic.  Row padding is never compared.  Nothing but the flags is
+ * written.  A stripe whose mask selects nothing gets all-zero flags and none of its
+ * memory is read.
+ *   Asynchronous on `stream`, scratch per (context, stream).  The masks may be
+ * reused or freed as soon as the call returns: they are copied through the
+ * stream's pinned staging, as the per-stripe descriptors of
+ * rs_decode_device_batch_masks are.  The staging waits for the copy that last read
+ * it and the device copy is reused in stream order, so two calls in flight on one
+ * stream do not overwrite each other's masks.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * d_recovery, d_mismatch or recovery_check -> RS_ERR_INVALID_ARGUMENT; rs_validate;
+ * the two row strides.  stripes == 0: RS_OK, nothing launched or written, the
+ * context not touched.  A batch in which no stripe selects a row: RS_OK, one
+ * hipMemsetAsync of the flags on `stream`; no kernel, no workspace, the context not
+ * touched.
+ *   Routes.  Every call first zeroes the flags on `stream`.  The default is the
+ * unfused route (RS_VERIFY_MASKS_FUSED_DEFAULT, measured below); rs_verify_set_fused
+ * and RS_MI355X_VERIFY_FUSED set this call's route together with
+ * rs_verify_device_batch's.
+ *   Fused (k_mono_verify_masks; the shapes of k_mono_verify): one launch per 65535
+ * stripes.  The destination map covers the union of the stripes' selected spans;
+ * the selection bytes are stripe b's, recovery_count apart.  A lane with nothing
+ * to compare loads a row and discards it; that row is the stripe's own first
+ * selected row (one word per stripe, loaded wave-uniformly), because the union's
+ * first row may be unselected in this stripe.  The workgroups of a stripe that
+ * selects nothing return before their first row load.
+ *   Unfused: every stripe's row list (recovery_count words apiece) and count are
+ * staged; where the batch encode is one launch the encode of the union span goes
+ * into scratch and k_verify_rows_masks compares (its grid covers the largest
+ * count, workgroups past a stripe's count leave at once); elsewhere stripe by
+ * stripe, each stripe's own span, stripes that select nothing skipped.
+ *   Measured (tools/verify_masks_time.py, profiles/verify_masks/verify_masks_time.txt;
+ * 1024:1024, a random 10 % of every stripe's rows unselected, us per call, median of 5
+ * rounds of 50 back-to-back calls; shared = rs_verify_device_batch /
+ * rs_locate_device_batch with every row selected, whose kernels are the parent
+ * commit's instruction for instruction -- the same leg on the parent's build in the
+ * same session read 239.60 / 124.95 (verify) and 230.29 / 124.77 (locate); spread =
+ * max - min of the shared leg's five rounds):
+ *     verify               masks fused  masks unfused  single calls  shared  spread
+ *     1 KiB, 64 stripes        270.96         251.52       1288.72   240.68    0.94
+ *     64 KiB, one stripe           --         127.20        118.78   120.36    4.26
+ *     locate               masks                                     shared  spread
+ *     1 KiB, 64 stripes        256.27                                230.13    0.73
+ *     64 KiB, one stripe       131.85                                124.40    0.70
+ * The fused masks verify was expected within the shared call's spread plus one small
+ * copy; it is NOT: +30.3 us.  Its kernel takes 247.9 us (it loads four selection
+ * bytes per lane, which the every-row shared call does not) and the staging copy and
+ * its two engine hand-overs take most of the rest.  It is also slower than the
+ * unfused masks route (251.5 us: the batch encode 196 us, k_verify_rows_masks 29
+ * us), so the DEFAULT for this call is the unfused route; rs_verify_set_fused(ctx,
+ * 1) and RS_MI355X_VERIFY_FUSED=1 still force the fused kernel.  Both are far below
+ * the 64 single calls (4.7x to 5.1x).  DESIGN.md 4.4k has the rest. */
+#define RS_VERIFY_MASKS_FUSED_DEFAULT 0
+rs_status rs_verify_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                       uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                       const void *d_original, uint64_t original_stride,
+                                       uint64_t original_stripe_stride, const void *d_recovery,
+                                       uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                       const uint8_t *recovery_check, uint8_t *d_mismatch, void *stream,
+                                       rs_error *err);
 
 /* ---- locate: which original of a stripe is corrupt? ----
  * rs_verify_device flags the recovery rows that disagree with the originals.
@@ -638,7 +712,7 @@ rs_status rs_verify_set_fused(rs_context *ctx, int mode);
  * 1 KiB and 14 us at 64 KiB.  The fused verify (10.55 / 240.5 us) stays the
  * cheaper first pass of a scrub that expects no corrupt originals.  DESIGN.md
  * "Locate" has the rest.
- *   Not covered: a mask per stripe; stripes with missing
+ *   Not covered: stripes with missing
  * originals (rs_locate_device_degraded below locates in those); the host
  * pipeline, the object API and the sharded classes; a fused
  * form on k_mono_verify.  (One corrupt original together with corrupt recovery
@@ -659,6 +733,50 @@ rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  uint64_t recovery_stride, uint64_t recovery_stripe_stride,
                                  const uint8_t *recovery_check, int32_t *d_located, uint8_t *d_mismatch, void *stream,
                                  rs_error *err);
+
+/* ---- locate with a mask per stripe ----
+ * rs_locate_device_batch with the per-stripe masks of
+ * rs_verify_device_batch_masks (HOST, stripes x recovery_count bytes, NOT NULL;
+ * copied through the stream's staging, free to reuse when the call returns).
+ * Everything else -- matrices, strides, d_mismatch, d_located, the table -- is the
+ * plain locate's.  Stripe b ends exactly as if rs_locate_device had been called on
+ * it with row b of the mask; a row its mask does not select is never read in that
+ * stripe.  Every byte of d_mismatch and every word of d_located is defined after
+ * the call; nothing else is written.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * d_recovery, d_located, d_mismatch or recovery_check -> RS_ERR_INVALID_ARGUMENT;
+ * rs_validate; the two row strides; stripes == 0: RS_OK; recovery_count < 2,
+ * original_count > RS_LOCATE_MAX_ORIGINALS or original_count x recovery_count >
+ * RS_LOCATE_MAX_COEFFICIENTS -> RS_ERR_INVALID_ARGUMENT.  Then every stripe's mask is
+ * counted on the host, in stripe order.  A stripe that selects fewer than two
+ * rows cannot be located, and
+ *   stripe_status == NULL: the call is all or nothing.  RS_ERR_INVALID_ARGUMENT with
+ *     the first such stripe's number in err->index; nothing is launched, nothing
+ *     is written.
+ *   stripe_status != NULL (HOST, `stripes` bytes): every stripe gets one rs_status,
+ *     RS_OK or RS_ERR_INVALID_ARGUMENT.  A stripe that cannot be located is skipped:
+ *     none of its rows is read, its flags are all 0 and d_located[b] =
+ *     RS_LOCATE_SKIPPED.  The others are located and the call returns RS_OK.
+ *   The table is the plain locate's, shared with it both ways: a warm stream builds
+ * none for either call.
+ *   Launches, per 65535 stripes: the unfused route of
+ * rs_verify_device_batch_masks, then k_locate_find_masks (j0, j1 and the count of
+ * selected rows are the stripe's; a skipped stripe's workgroup stores
+ * RS_LOCATE_SKIPPED and reads nothing of it) and k_locate_confirm_masks (its grid
+ * covers the largest count).
+ *   Measured (tools/verify_masks_time.py, profiles/verify_masks/): see DESIGN.md
+ * §4.4k.
+ *   Not covered: per-stripe masks for rs_heal_device*, the robust and the degraded
+ * calls; a fused form on k_mono_verify_masks; the host pipeline, the object API
+ * and the sharded classes. */
+#define RS_LOCATE_SKIPPED (-4)
+rs_status rs_locate_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                       uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                       const void *d_original, uint64_t original_stride,
+                                       uint64_t original_stripe_stride, const void *d_recovery,
+                                       uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                       const uint8_t *recovery_check, int32_t *d_located, uint8_t *d_mismatch,
+                                       uint8_t *stripe_status, void *stream, rs_error *err);
 
 /* ---- robust locate: one corrupt original among corrupt recovery rows ----
  * rs_locate_device needs every selected recovery row but the damage of the one

@@ -175,6 +175,10 @@ struct UpdateWs {
 struct VerifyWs {
     DevBuf enc, d_mask;
     PinnedBuf h_mask;
+    // rs_verify_device_batch_masks / rs_locate_device_batch_masks: a call's per-stripe
+    // selections (or row lists and counts), staged anew by every call
+    DevBuf d_masks;
+    PinnedBuf h_masks;
     std::vector<uint8_t> mask;  // what d_mask was built from, as 0/1 bytes
     bool mask_valid = false;
 };
@@ -408,6 +412,9 @@ struct rs_context {
     // single-chunk column kernel (rs_verify_set_fused, RS_MI355X_VERIFY_FUSED; the
     // default is measured: DESIGN.md "Verify")
     bool verify_fused = RS_VERIFY_FUSED_DEFAULT != 0;
+    // rs_verify_device_batch_masks: its own default (measured: DESIGN.md §4.4k); rs_verify_set_fused
+    // and RS_MI355X_VERIFY_FUSED force both
+    bool verify_masks_fused = RS_VERIFY_MASKS_FUSED_DEFAULT != 0;
     // the pass kernels' tables as 8-word bases (rs_kernels.hip BasisStager; RS_MI355X_PASS_BASIS=1).
     // Off by default: within +-2.5 % of the 20-word tables on 9 pass shapes, slower on the small
     // ones (4096:4096 x 1 KiB decode 100 % 39.4 -> 40.3 us, 8192:8192 x 64 KiB encode 1028 ->
@@ -2143,6 +2150,170 @@ void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
     }
 }
 
+// ---- verify and locate with a mask per stripe (rs_*_device_batch_masks) ----
+// What the host keeps of stripe b's mask: the span of its selected rows and their
+// number (nsel = 0: the stripe is left alone -- nothing selected, or a locate skips it).
+struct StripeSel {
+    uint32_t lo, hi, nsel;
+};
+
+StripeSel stripe_sel(const uint8_t *mask, uint32_t M) {
+    StripeSel r{M, 0, 0};
+    for (uint32_t j = 0; j < M; ++j)
+        if (mask[j]) r.lo = std::min(r.lo, j), r.hi = j + 1, ++r.nsel;
+    return r;
+}
+
+// The union span and the largest count of stripes [b0, b1).
+StripeSel union_sel(const std::vector<StripeSel> &sel, uint64_t b0, uint64_t b1, uint32_t M) {
+    StripeSel u{M, 0, 0};
+    for (uint64_t b = b0; b < b1; ++b)
+        if (sel[b].nsel) u.lo = std::min(u.lo, sel[b].lo), u.hi = std::max(u.hi, sel[b].hi), u.nsel = std::max(u.nsel, sel[b].nsel);
+    return u;
+}
+
+bool verify_column(rs_context *ctx, bool high, const Geom &g, uint64_t N, uint64_t M, uint32_t *L_out) {
+    const uint32_t n = uint32_t(next_pow2(high ? M : N)), L = ilog2(n);
+    const uint32_t C = uint32_t(((high ? N : M) + n - 1) / n);
+    *L_out = L;
+    return use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+}
+
+// The fused route: the stripes' selection bytes and first-row words go through the
+// stream's staging (VerifyWs::h_masks -> d_masks; the staging waits for the copy that
+// last read it, and the device buffer is reused in stream order), then one launch per
+// kMaxBatchStripes stripes over the union of their spans.  V.mask: stripes x M bytes.
+void verify_masks_fused(rs_context *ctx, Workspace &ws, bool high, Geom g, const VerifyCall &V,
+                        const std::vector<StripeSel> &sel, uint32_t L, hipStream_t s) {
+    const uint32_t M = uint32_t(V.M);
+    if (!ws.ver) ws.ver.reset(new VerifyWs);
+    VerifyWs &v = *ws.ver;
+    const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+    for (uint64_t b0 = 0; b0 < V.stripes; b0 += kMaxBatchStripes) {  // grid.y limit
+        const uint64_t nb = std::min<uint64_t>(kMaxBatchStripes, V.stripes - b0);
+        const StripeSel u = union_sel(sel, b0, b0 + nb, M);
+        if (!u.nsel) continue;  // (the flags are zero already)
+        const size_t first_off = round_up(nb * M, 4), bytes = first_off + nb * 4;
+        uint8_t *h = v.h_masks.get(bytes);
+        uint32_t *first = reinterpret_cast<uint32_t *>(h + first_off);
+        uint64_t rows = 0;
+        uint32_t has_empty = 0;
+        for (uint64_t b = 0; b < nb; ++b) {
+            const uint8_t *m = V.mask + (b0 + b) * M;
+            for (uint32_t j = 0; j < M; ++j) h[b * M + j] = m[j] != 0;
+            first[b] = sel[b0 + b].nsel ? sel[b0 + b].lo - u.lo : rs::kVerifyNoRow;
+            rows += sel[b0 + b].nsel ? V.N + sel[b0 + b].nsel : 0;
+            if (!sel[b0 + b].nsel) has_empty = 1;
+        }
+        uint8_t *d = static_cast<uint8_t *>(v.d_masks.get(bytes));
+        check(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+        v.h_masks.copied_on(s);
+        g.stripes = uint32_t(nb);
+        rs::MonoVerifyMaskArgs A;
+        static_cast<rs::MonoCore &>(A) = mono_args(ctx, L, g, true);
+        A.src[0] = rs::RowMap{V.d_orig + b0 * V.orig_bstride, g.orig(), 0, uint32_t(V.N)};
+        A.src_bstride[0] = V.orig_bstride;
+        A.nsrc = 1;
+        A.dst = rs::RowMap{V.d_rec + b0 * V.rec_bstride + uint64_t(u.lo) * g.rec(), g.rec(), u.lo, u.hi};
+        A.dst_bstride = V.rec_bstride;
+        A.chunks = 1;
+        A.ifft_img = high ? 1 : 0;  // as encode_high / encode_low
+        A.fft_img = high ? 0 : 1;
+        A.ifft_img_step = high ? 1 : 0;
+        A.fft_img_step = high ? 0 : 1;
+        A.flags = V.d_flags + b0 * V.M + u.lo;
+        A.flag_bstride = V.M;
+        A.sel = d + u.lo;
+        A.sel_bstride = V.M;
+        A.first = reinterpret_cast<const uint32_t *>(d + first_off);
+        A.has_empty = has_empty;
+        update_launch(s, rows * pack_bytes, [&] { return rs::launch_mono_verify_masks(int(L), A, s); });
+    }
+}
+
+// The unfused route, and behind it (d_located) the plain locate's two launches: every
+// stripe's row list (M words apiece) and the counts go through the stream's staging in
+// one copy.  Where the batch encode is one launch the encode of the union span goes
+// into scratch for every run of consecutive stripes with sel[b].nsel != 0 (the whole
+// group when no stripe is left alone), then one compare per run, and one find and one
+// confirm for the group; elsewhere stripe by stripe, each with its own span, and a
+// stripe with sel[b].nsel = 0 costs no encode and no compare.  The caller has zeroed
+// the flags.
+void masks_unfused(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const VerifyCall &V,
+                   const std::vector<StripeSel> &sel, bool column, int32_t *d_located, const uint16_t *logs,
+                   hipStream_t s) {
+    const uint32_t M = uint32_t(V.M);
+    if (!ws.ver) ws.ver.reset(new VerifyWs);
+    VerifyWs &v = *ws.ver;
+    const size_t words = size_t(V.stripes) * M + V.stripes;
+    uint32_t *h = reinterpret_cast<uint32_t *>(v.h_masks.get(words * 4));
+    uint32_t *hc = h + size_t(V.stripes) * M;
+    for (uint64_t b = 0; b < V.stripes; ++b) {
+        const uint8_t *m = V.mask + b * M;
+        uint32_t *list = h + b * M, k = 0;
+        for (uint32_t j = 0; j < M; ++j) {
+            list[j] = 0;
+            if (sel[b].nsel && m[j]) list[k++] = j;
+        }
+        hc[b] = k;
+    }
+    uint32_t *d = static_cast<uint32_t *>(v.d_masks.get(words * 4));
+    check(hipMemcpyAsync(d, h, words * 4, hipMemcpyHostToDevice, s));
+    v.h_masks.copied_on(s);
+    const uint32_t *d_lists = d, *d_counts = d + size_t(V.stripes) * M;
+
+    const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+    const uint64_t W = g.stride, group = column ? kMaxBatchStripes : 1;
+    uint8_t *enc = static_cast<uint8_t *>(v.enc.get(std::min<uint64_t>(group, V.stripes) * V.M * W));
+    Geom ge = g;
+    ge.rec_stride = W;
+    ge.orig_bstride = V.orig_bstride;
+    ge.rec_bstride = V.M * W;
+    for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
+        const uint64_t b1 = b0 + std::min<uint64_t>(group, V.stripes - b0);
+        // the encode and the compare over every run of consecutive stripes that select
+        // something (a batch without left-alone stripes is one run): the encode reads
+        // the originals, and nothing of a left-alone stripe is read
+        for (uint64_t r0 = b0, r1; r0 < b1; r0 = r1) {
+            r1 = r0 + 1;
+            if (!sel[r0].nsel) continue;
+            while (r1 < b1 && sel[r1].nsel) ++r1;
+            const StripeSel u = union_sel(sel, r0, r1, M);
+            ge.stripes = uint32_t(r1 - r0);
+            uint8_t *want = enc + (r0 - b0) * V.M * W;
+            const uint8_t *o = V.d_orig + r0 * V.orig_bstride;
+            if (high) encode_high(ctx, ws, ge, V.N, V.M, o, want, s, u.lo, u.hi);
+            else encode_low(ctx, ws, ge, V.N, V.M, o, want, s, u.lo, u.hi);
+            rs::VerifyRowsMaskArgs R;
+            R.want = want, R.want_stride = W, R.want_bstride = V.M * W;
+            R.have = V.d_rec + r0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
+            R.rows = d_lists + r0 * M, R.list_stride = M, R.counts = d_counts + r0;
+            R.nrows = u.nsel, R.packs = g.packs, R.stripes = ge.stripes;
+            R.flags = V.d_flags + r0 * V.M, R.flag_bstride = V.M;
+            R.fmt = g.fmt;
+            update_launch(s, 2 * uint64_t(u.nsel) * pack_bytes * ge.stripes,
+                          [&] { return rs::launch_verify_rows_masks(R, s); });
+        }
+        if (!d_located) continue;
+        // one find and one confirm for the group, as the plain locate's
+        const StripeSel u = union_sel(sel, b0, b1, M);
+        rs::LocateMaskArgs A;
+        A.want = enc, A.want_stride = W, A.want_bstride = V.M * W;
+        A.have = V.d_rec + b0 * V.rec_bstride, A.have_stride = g.rec(), A.have_bstride = V.rec_bstride;
+        A.rows = d_lists + b0 * M, A.list_stride = M, A.counts = d_counts + b0;
+        A.nsel = u.nsel, A.packs = g.packs, A.stripes = uint32_t(b1 - b0);
+        A.N = uint32_t(V.N), A.M = M;
+        A.flags = V.d_flags + b0 * V.M, A.flag_bstride = V.M;
+        A.located = d_located + b0;
+        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
+        A.fmt = g.fmt;
+        update_launch(s, (V.M + 4) * uint64_t(A.stripes), [&] { return rs::launch_locate_find_masks(A, s); });
+        if (u.nsel >= 2)
+            update_launch(s, 2 * uint64_t(u.nsel) * pack_bytes * A.stripes,
+                          [&] { return rs::launch_locate_confirm_masks(A, s); });
+    }
+}
+
 // What rs_locate_device_robust* adds to a locate (DESIGN.md "Robust locate").
 struct RobustCall {
     uint32_t max_outliers;
@@ -2669,7 +2840,7 @@ rs_status rs_context_create(int device, rs_context **out) {
         if (const char *qs = getenv("RS_MI355X_QUAD")) ctx->quad = qs[0] == '1';
         if (const char *cp = getenv("RS_MI355X_COPYIN_POOL")) ctx->copyin_pool = cp[0] == '1';
         if (const char *ud = getenv("RS_MI355X_UPDATE_DIRECT_MAX")) ctx->update_direct_max = uint32_t(strtoul(ud, nullptr, 10));
-        if (const char *vf = getenv("RS_MI355X_VERIFY_FUSED")) ctx->verify_fused = atoi(vf) != 0;
+        if (const char *vf = getenv("RS_MI355X_VERIFY_FUSED")) ctx->verify_fused = ctx->verify_masks_fused = atoi(vf) != 0;
         ctx->quad_default = ctx->quad;
         if (const char *de = getenv("RS_MI355X_DENSE")) ctx->dense = de[0] == '1';
         ctx->dense_default = ctx->dense;
@@ -3408,10 +3579,57 @@ rs_status rs_verify_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M
                                   d_mismatch, stream, err);
 }
 
+rs_status rs_verify_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                       uint64_t stripes, const void *d_orig, uint64_t orig_stride,
+                                       uint64_t orig_stripe_stride, const void *d_rec, uint64_t rec_stride,
+                                       uint64_t rec_stripe_stride, const uint8_t *recovery_check, uint8_t *d_mismatch,
+                                       void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_mismatch) || !recovery_check)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        // every stripe's mask, in stripe order, before any device work
+        std::vector<StripeSel> sel(stripes);
+        bool any = false;
+        for (uint64_t b = 0; b < stripes; ++b) {
+            sel[b] = stripe_sel(recovery_check + b * M, uint32_t(M));
+            any = any || sel[b].nsel;
+        }
+        auto s = static_cast<hipStream_t>(stream);
+        if (!any) {
+            // no row to check in any stripe: every flag is 0.  One memset on the caller's
+            // stream; no kernel, no workspace, the context not touched
+            check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
+            return set_err(err, RS_OK);
+        }
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                     0, 0, recovery_check, d_mismatch};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        StreamWs sw(ctx, s);
+        // every flag is defined after the call: zero, then the kernels store the ones
+        check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
+        uint32_t L = 0;
+        const bool column = verify_column(ctx, high != 0, g, N, M, &L);
+        if (column && ctx->verify_masks_fused) verify_masks_fused(ctx, sw.w, high != 0, g, V, sel, L, s);
+        else masks_unfused(ctx, sw.w, high != 0, g, V, sel, column, nullptr, nullptr, s);
+        return set_err(err, RS_OK);
+    });
+}
+
 rs_status rs_verify_set_fused(rs_context *ctx, int mode) {
     if (!ctx) return RS_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->verify_fused = mode != 0;
+    ctx->verify_fused = ctx->verify_masks_fused = mode != 0;
     return RS_OK;
 }
 
@@ -3460,6 +3678,54 @@ rs_status rs_locate_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M
                            rs_error *err) {
     return rs_locate_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
                                   d_located, d_mismatch, stream, err);
+}
+
+rs_status rs_locate_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                       uint64_t stripes, const void *d_orig, uint64_t orig_stride,
+                                       uint64_t orig_stripe_stride, const void *d_rec, uint64_t rec_stride,
+                                       uint64_t rec_stripe_stride, const uint8_t *recovery_check, int32_t *d_located,
+                                       uint8_t *d_mismatch, uint8_t *stripe_status, void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_located) || !ptr_ok(d_mismatch) || !recovery_check)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    if (M < 2 || N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    return guarded(err, [&]() -> rs_status {
+        // every stripe's mask, in stripe order, before any device work: a ratio needs two rows
+        std::vector<StripeSel> sel(stripes);
+        for (uint64_t b = 0; b < stripes; ++b) {
+            sel[b] = stripe_sel(recovery_check + b * M, uint32_t(M));
+            if (stripe_status) stripe_status[b] = sel[b].nsel < 2 ? RS_ERR_INVALID_ARGUMENT : RS_OK;
+            if (sel[b].nsel >= 2) continue;
+            if (!stripe_status) {
+                set_err(err, RS_ERR_INVALID_ARGUMENT);
+                if (err) err->index = b;
+                return RS_ERR_INVALID_ARGUMENT;
+            }
+            sel[b] = StripeSel{uint32_t(M), 0, 0};  // skipped: none of its rows is read
+        }
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                     0, 0, recovery_check, d_mismatch};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        const uint16_t *logs = locate_table(ctx, sw.w, high != 0, N, M, s);
+        check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
+        uint32_t L = 0;
+        const bool column = verify_column(ctx, high != 0, g, N, M, &L);
+        masks_unfused(ctx, sw.w, high != 0, g, V, sel, column, d_located, logs, s);
+        return set_err(err, RS_OK);
+    });
 }
 
 // ---- robust locate: one corrupt original among corrupt recovery rows (include/rs_mi355x.h) ----

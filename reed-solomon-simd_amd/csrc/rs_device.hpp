@@ -483,6 +483,24 @@ struct MonoVerifyArgs : MonoCore {
 // 4, grid.y = A.stripes (>= 1).  The staged body is the same for both rates (they
 // differ in the images the host names), so one kernel per (L, elems) serves both.
 hipError_t launch_mono_verify(int L, const MonoVerifyArgs &A, hipStream_t stream);
+// The fused route with one selection PER STRIPE (k_mono_verify_masks, rs_verify_device_batch_masks):
+// dst is narrowed to the union of the stripes' selected spans, sel (not nullptr) points at
+// stripe 0's selection byte of row dst.row_begin and stripe b's bytes sit b * sel_bstride
+// further.  Row dst.row_begin need not be selected in every stripe, so the row a lane
+// without a row of its own reads and discards is the stripe's: first[b] = the stripe's
+// first selected row minus dst.row_begin, or kVerifyNoRow where the stripe selects
+// nothing -- its workgroups return before their first row load.
+constexpr uint32_t kVerifyNoRow = 0xFFFFFFFFu;
+struct MonoVerifyMaskArgs : MonoVerifyArgs {
+    uint64_t sel_bstride = 0;
+    const uint32_t *first = nullptr;  // one word per stripe
+    // some first[b] is kVerifyNoRow: only then do the workgroups wait for their word
+    // ahead of the row loads (a dependent scalar load in front of every workgroup's
+    // prologue otherwise); without one the word is first needed behind them
+    uint32_t has_empty = 0;
+};
+// As launch_mono_verify; one launch for the A.stripes <= 65535 stripes.
+hipError_t launch_mono_verify_masks(int L, const MonoVerifyMaskArgs &A, hipStream_t stream);
 // The unfused route's compare (k_verify_rows): for r < nrows and every pack, row
 // j = rows ? rows[r] : r of `want` (the encode in scratch) against row j of `have`
 // (the caller's recovery matrix), both in the layout of fmt; a difference stores
@@ -498,6 +516,14 @@ struct VerifyRowsArgs {
     ShardFormat fmt;
 };
 hipError_t launch_verify_rows(const VerifyRowsArgs &A, hipStream_t stream);
+// The compare with one row list PER STRIPE (k_verify_rows_masks): stripe b's rows are
+// rows[b * list_stride + r], r < counts[b]; nrows = the largest count (the grid's y:
+// workgroups past a stripe's count leave at once, a stripe with count 0 reads nothing).
+struct VerifyRowsMaskArgs : VerifyRowsArgs {
+    uint64_t list_stride = 0;
+    const uint32_t *counts = nullptr;  // one word per stripe
+};
+hipError_t launch_verify_rows_masks(const VerifyRowsMaskArgs &A, hipStream_t stream);
 
 // ---- locate (rs_locate_device*, rs_locate.hip; DESIGN.md "Locate") ----------
 // The coefficient step over a slab of consecutive originals i0 .. i0 + count - 1:
@@ -536,6 +562,18 @@ struct LocateArgs {
 };
 hipError_t launch_locate_find(const LocateArgs &A, hipStream_t stream);
 hipError_t launch_locate_confirm(const LocateArgs &A, hipStream_t stream);
+// The two launches with one row list PER STRIPE (k_locate_find_masks,
+// k_locate_confirm_masks; rs_locate_device_batch_masks): stripe b's selected rows are
+// rows[b * list_stride + r], r < counts[b], in order; nsel = the largest count (the
+// confirm's grid).  A stripe with counts[b] < 2 is skipped: the find stores
+// kLocateSkipped, the confirm leaves, neither reads a row of it.
+constexpr int32_t kLocateSkipped = -4;  // include/rs_mi355x.h RS_LOCATE_SKIPPED
+struct LocateMaskArgs : LocateArgs {
+    uint64_t list_stride = 0;
+    const uint32_t *counts = nullptr;  // one word per stripe
+};
+hipError_t launch_locate_find_masks(const LocateMaskArgs &A, hipStream_t stream);
+hipError_t launch_locate_confirm_masks(const LocateMaskArgs &A, hipStream_t stream);
 
 // ---- degraded locate (rs_locate_device_degraded*, rs_locate.hip; DESIGN.md "Degraded locate") ----
 // map: N words, map[p] = p where original p is present, else N + the reference

@@ -15,6 +15,9 @@
 //   k_locate_confirm   D_j == (D_j0 / G[j0][i]) * G[j][i] over every selected row and
 //                      pack of the stripes that name an i; a refutation stores
 //                      RS_LOCATE_UNKNOWN
+//   k_locate_find_masks / k_locate_confirm_masks   the two with a row list and a count
+//                      per stripe (rs_locate_device_batch_masks); a
+//                      stripe with fewer than two rows is skipped unread
 //
 // and of a heal (rs_heal_device*, DESIGN.md "Heal"), after the confirm and while
 // the encode is still in scratch:
@@ -239,6 +242,109 @@ __global__ __launch_bounds__(256) void k_locate_confirm(const LocateArgs A) {
     if (refuted) A.located[b] = kLocateUnknown;  // every refuting lane stores the same word
 }
 
+// k_locate_find with stripe b's own row list (rs_device.hpp LocateMaskArgs): j0, j1 and
+// the count of selected rows are the stripe's.  A stripe that selects fewer than two
+// rows is skipped before anything of it is read, its flags included.
+__global__ __launch_bounds__(kFindThreads) void k_locate_find_masks(const LocateMaskArgs A) {
+    __shared__ uint32_t s_count, s_pack, s_found;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t b = blockIdx.x;
+    const uint32_t nsel = A.counts[b];
+    if (nsel < 2) {
+        if (tid == 0) A.located[b] = kLocateSkipped;
+        return;
+    }
+    if (tid == 0) s_count = 0, s_pack = 0xFFFFFFFFu, s_found = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint8_t *flags = A.flags + b * A.flag_bstride;
+    uint32_t c = 0;
+    for (uint32_t j = tid; j < A.M; j += kFindThreads) c += flags[j] != 0;
+    if (c) atomicAdd(&s_count, c);
+    __syncthreads();
+    const uint32_t differ = s_count;
+    if (differ < nsel) {
+        if (tid == 0) A.located[b] = differ ? kLocateRows : kLocateClean;
+        return;
+    }
+    const uint32_t *rows = A.rows + b * A.list_stride;
+    const uint32_t j0 = rows[0], j1 = rows[1];
+    const uint8_t *want = A.want + b * A.want_bstride, *have = A.have + b * A.have_bstride;
+    for (uint32_t base = 0; base < A.packs; base += kFindThreads * kFindUnroll) {
+        uint32_t first = 0xFFFFFFFFu;
+#pragma unroll
+        for (uint32_t k = kFindUnroll; k-- > 0;) {
+            const uint32_t pk = base + k * kFindThreads + tid;
+            uint32_t dl = 0, dh = 0;
+            if (pk < A.packs) ld_syndrome(A, want, have, j0, pack_io(A.fmt, pk), dl, dh);
+            if (dl | dh) first = pk;
+        }
+        if (__syncthreads_or(first != 0xFFFFFFFFu)) {
+            if (first != 0xFFFFFFFFu) atomicMin(&s_pack, first);
+            break;
+        }
+    }
+    __syncthreads();
+    const uint32_t pk = s_pack;
+    int32_t result = kLocateUnknown;
+    if (pk < A.packs) {
+        const PackIO io = pack_io(A.fmt, pk);
+        uint32_t l0, h0, l1, h1;
+        ld_syndrome(A, want, have, j0, io, l0, h0);
+        ld_syndrome(A, want, have, j1, io, l1, h1);
+        uint32_t k = 0;
+        while (k < 3 && !(((l0 | h0) >> (8 * k)) & 0xFFu)) ++k;
+        const uint32_t d0 = ((l0 >> (8 * k)) & 0xFFu) | ((h0 >> (8 * k)) & 0xFFu) << 8;
+        const uint32_t d1 = ((l1 >> (8 * k)) & 0xFFu) | ((h1 >> (8 * k)) & 0xFFu) << 8;
+        if (d0 && d1) {
+            const uint32_t ratio = (uint32_t(A.log_table[d1]) + 65535u - A.log_table[d0]) % 65535u;
+            const uint16_t *r0 = A.logs + uint64_t(j0) * A.N, *r1 = A.logs + uint64_t(j1) * A.N;
+            for (uint32_t i = tid; i < A.N; i += kFindThreads) {
+                const uint32_t g0 = r0[i], g1 = r1[i];
+                if (g0 != kNoLog && g1 != kNoLog && (g1 + 65535u - g0) % 65535u == ratio) atomicMin(&s_found, i);
+            }
+            __syncthreads();
+            if (s_found < A.N) result = int32_t(s_found);
+        }
+    }
+    if (tid == 0) A.located[b] = result;
+}
+
+// k_locate_confirm with stripe b's own row list and count; the grid's row groups
+// cover the batch's largest count, and a group past its stripe's count has no row.
+__global__ __launch_bounds__(256) void k_locate_confirm_masks(const LocateMaskArgs A) {
+    const uint64_t b = blockIdx.z;
+    const int32_t loc = __builtin_amdgcn_readfirstlane(A.located[b]);
+    if (loc < 0) return;  // clean, ROWS, unknown, skipped, or refuted by another workgroup already
+    const ConstWords logs = const_words(A.logs), lut = const_words(A.lut);
+    const ConstWords rows = const_words(A.rows + b * A.list_stride);
+    const uint32_t nsel = const_words(A.counts)[b];
+    const uint32_t r0 = blockIdx.y * A.rows_per_group;
+    const uint32_t r1 = r0 + A.rows_per_group < nsel ? r0 + A.rows_per_group : nsel;
+    if ((r0 ? r0 : 1u) >= r1) return;
+    const uint32_t pk = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = pk < A.packs;
+    const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
+    const uint8_t *want = A.want + b * A.want_bstride, *have = A.have + b * A.have_bstride;
+    uint32_t el, eh;  // e = D_j0 / G[j0][i], once per workgroup
+    locate_error(A, logs, lut, rows[0], uint32_t(loc), want, have, io, ok, el, eh);
+    bool refuted = false;
+    for (uint32_t r = r0 ? r0 : 1u; r < r1; ++r) {  // entry 0 is row j0 itself
+        const uint32_t j = rows[r];
+        const uint32_t lg = coef_log(logs, A.N, j, uint32_t(loc));
+        uint32_t dl = 0, dh = 0;
+        if (ok) ld_syndrome(A, want, have, j, io, dl, dh);
+        uint32_t pl = 0, ph = 0;
+        if (lg != kNoLog) {
+            uint32_t t[kTableWords];
+#pragma unroll
+            for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(lg) * kTableWords + w];
+            gf_muladd4(pl, ph, el, eh, t);
+        }
+        refuted |= pl != dl || ph != dh;
+    }
+    if (refuted) A.located[b] = kLocateUnknown;  // every refuting lane stores the same word
+}
+
 // The confirm's grid.  Every branch but the pack bound is uniform over the
 // workgroup; a stripe with nothing to heal (the common one of a scrub) leaves at once.
 __global__ __launch_bounds__(256) void k_heal(const HealArgs A) {
@@ -424,6 +530,29 @@ hipError_t launch_locate_confirm(const LocateArgs &A0, hipStream_t s) {
     if (grid.y > 65535) return hipErrorInvalidValue;
     k_locate_confirm<<<grid, threads, 0, s>>>(A);
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_confirm");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_find_masks(const LocateMaskArgs &A, hipStream_t s) {
+    if (!A.stripes) return hipSuccess;
+    if (!A.rows || !A.counts || A.nsel > A.M || !A.packs || !A.N) return hipErrorInvalidValue;
+    k_locate_find_masks<<<dim3(A.stripes), kFindThreads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_find_masks");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_confirm_masks(const LocateMaskArgs &A0, hipStream_t s) {
+    if (!A0.stripes) return hipSuccess;
+    if (!A0.rows || !A0.counts || A0.nsel < 2 || !A0.packs || A0.stripes > 65535) return hipErrorInvalidValue;
+    LocateMaskArgs A = A0;
+    // the confirm's grid (launch_locate_confirm) over the largest count
+    const uint32_t threads = A.packs >= 256 ? 256u : (A.packs + 63u) / 64u * 64u, tiles = (A.packs + threads - 1) / threads;
+    const uint64_t units = uint64_t(A.nsel) * tiles * A.stripes;
+    A.rows_per_group = uint32_t(units / 1024 < 1 ? 1 : units / 1024 > 16 ? 16 : units / 1024);
+    const dim3 grid(tiles, (A.nsel + A.rows_per_group - 1) / A.rows_per_group, A.stripes);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    k_locate_confirm_masks<<<grid, threads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_locate_confirm_masks");
     return hipGetLastError();
 }
 

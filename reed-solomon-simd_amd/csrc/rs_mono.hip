@@ -757,6 +757,16 @@ struct VerifyPre {
     uint32_t ok = 0;         // bit j: word j belongs to a row of A.dst that is compared
     uint32_t have[2 << LR];  // the caller's word j
 };
+// A verify with a selection per stripe (k_mono_verify_masks, rs_device.hpp
+// MonoVerifyMaskArgs) adds the stripe's word of `first` and the row it names: the row
+// a lane with nothing to compare reads and discards, since row A.dst.row_begin may be
+// unselected in this stripe.  A type of its own, so that the other instantiations'
+// VerifyPre is what it was.
+template <int LR>
+struct VerifyPreMasks : VerifyPre<LR> {
+    uint32_t first = 0;
+    const uint8_t *safe = nullptr;
+};
 
 // Decode: does this wave hold, after the FFT's remap, any row of A.dst (TWO: or of d2)?
 // (there the wave's rows are one block of 2^IW consecutive rows)
@@ -1085,6 +1095,9 @@ __device__ __forceinline__ void reveal_issue(const MonoCore &A, const uint32_t *
 // selected reads row A.dst.row_begin (selected by contract: the host narrows the
 // map to the selected span) and discards it -- no branch around the loads (see
 // issue_col), and an unselected row is never read.
+// (VMASKS, k_mono_verify_masks: a selection per stripe.  The map is the union of the
+// stripes' spans and its first row may be unselected in this stripe, so the discarded
+// load goes to the stripe's own first selected row, vp.safe.)
 template <int L, int LR, int SPLIT>
 __device__ __forceinline__ void verify_select(const MonoCore &A, VerifyPre<LR> &vp, uint32_t lane, uint32_t wave) {
     using S = SeqOf<L, LR, true, SPLIT>;
@@ -1103,9 +1116,9 @@ __device__ __forceinline__ void verify_select(const MonoCore &A, VerifyPre<LR> &
         });
     }
 }
-template <int L, int LR, int SPLIT, int E>
+template <int L, int LR, int SPLIT, int E, typename VP>
 __device__ __forceinline__ void verify_issue(const MonoCore &A, const PackIO &io, const StripeBases &sb,
-                                             VerifyPre<LR> &vp, uint32_t lane, uint32_t wave) {
+                                             VP &vp, uint32_t lane, uint32_t wave) {
     using S = SeqOf<L, LR, true, SPLIT>;
     constexpr int I = S::v.count;
     const uint32_t span = A.dst.row_end - A.dst.row_begin;
@@ -1113,12 +1126,16 @@ __device__ __forceinline__ void verify_issue(const MonoCore &A, const PackIO &io
     const uint32_t r0 = paired_row<S, I, LR>(lane, wave, 0);
     const uint8_t *const p0 = map_base(A.dst, sb.dst, r0);  // (see row_at)
     vp.ok = 0;
+    // (the stripe's word of `first` is first needed here, behind the row and table loads)
+    if constexpr (std::is_same_v<VP, VerifyPreMasks<LR>>) vp.safe = sb.dst + uint64_t(vp.first) * A.dst.stride;
     static_for<0, (2 << LR)>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         constexpr uint32_t D = paired_delta<S, I, LR>(j);
         const bool ok = r0 + D - A.dst.row_begin < span && vp.sl[j] != 0;
         vp.ok |= uint32_t(ok) << j;
-        const uint8_t *p = ok ? p0 + uint64_t(D) * A.dst.stride : sb.dst;
+        const uint8_t *p;
+        if constexpr (std::is_same_v<VP, VerifyPreMasks<LR>>) p = ok ? p0 + uint64_t(D) * A.dst.stride : vp.safe;
+        else p = ok ? p0 + uint64_t(D) * A.dst.stride : sb.dst;
         if constexpr (E == 2) vp.have[j] = ld_half(p + off, io);
         else vp.have[j] = ld_word(p + off, io);
     });
@@ -2035,6 +2052,8 @@ using MonoArgM = std::conditional_t<MASKS, MonoMaskArgs, MonoArgT<MODE, STAGED>>
 // with MASKS, k_mono_repair_masks: KA = MonoMaskArgs2)
 // VERIFY (k_mono_verify, rs_verify.hip): the staged encode whose store_col compares
 // with the caller's rows and sets flags instead of storing (KA = MonoVerifyArgs)
+// VMASKS (k_mono_verify_masks, a form of VERIFY): a selection per stripe, and the
+// stripe's own row for the discarded loads (KA = MonoVerifyMaskArgs)
 // PRE (k_mono's encode entry, RS_MONO_PRELOAD): K was put together by the kernel entry
 // from plain leading parameters, which arrive in SGPRs with the wave (kernel-argument
 // preload), and the rest of MonoCore, which is loaded from the argument segment.
@@ -2049,12 +2068,14 @@ template <int L, int LR, int MODE, bool STAGED, bool BATCH, bool SPLIT, int E, b
           bool VERIFY = false, bool PRE = false, bool DENSE = false, typename KA = MonoArgM<MODE, STAGED, MASKS>>
 __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const MonoLead *lead = nullptr,
                                           [[maybe_unused]] const MonoLeadDense *dense = nullptr) {
+    constexpr bool VMASKS = std::is_same_v<KA, MonoVerifyMaskArgs>;  // (the argument type says it)
     static_assert(!DENSE || PRE, "dense rows: a form of the preloaded encode entry");
     static_assert(!PRE || (STAGED && !SPLIT && !MASKS && !TWO && !VERIFY &&
                            (MODE == kMonoEncodeHigh || MODE == kMonoEncodeLow)),
                   "preloaded arguments: the staged single-chunk encode");
     static_assert(!VERIFY || (STAGED && !MASKS && !TWO && (MODE == kMonoEncodeHigh || MODE == kMonoEncodeLow)),
                   "verify: the staged single-chunk encode");
+    static_assert(!VMASKS || (VERIFY && BATCH), "a selection per stripe: the verify's batch form");
     // (MASKS and TWO together, k_mono_repair_masks: MASKS' own conditions below hold)
     static_assert(!TWO || MODE == kMonoDecode || (!MASKS && MODE == kMonoHalfFDec), "second destination: decodes");
     static_assert(!MASKS || (MODE == kMonoDecode && STAGED && BATCH && !SPLIT),
@@ -2207,10 +2228,19 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
         d2.m = K.dst2;
         d2.base = const_cast<uint8_t *>(K.dst2.base) + (BATCH ? uint64_t(blockIdx.y) * K.dst2_bstride : 0);
     }
-    VerifyPre<LR> vp;
+    std::conditional_t<VMASKS, VerifyPreMasks<LR>, VerifyPre<LR>> vp;
     if constexpr (VERIFY) {
         vp.flags = K.flags + (BATCH ? uint64_t(blockIdx.y) * K.flag_bstride : 0);
         vp.sel = K.sel;
+    }
+    // VMASKS (k_mono_verify_masks, KA = MonoVerifyMaskArgs): the stripe's own selection
+    // bytes, and its word of `first` -- constant for the kernel's lifetime and at a
+    // wave-uniform address (blockIdx.y): a scalar load of the constant address space,
+    // requested here and waited for behind verify_select's requests
+    if constexpr (VMASKS) {
+        typedef const __attribute__((address_space(4))) uint32_t *cptr;
+        vp.sel = K.sel + uint64_t(blockIdx.y) * K.sel_bstride;
+        vp.first = ((cptr)(reinterpret_cast<uintptr_t>(K.first)))[blockIdx.y];
     }
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2467,6 +2497,17 @@ __device__ __forceinline__ void mono_body(const KA &K, [[maybe_unused]] const Mo
                 issue_shared();
             } else if constexpr (!DEC) {
                 if constexpr (VERIFY) verify_select<L, LR, PK>(A, vp, lane, wave);
+                if constexpr (VMASKS) {
+                    // a stripe that selects nothing is left alone: none of its rows is
+                    // read, nothing of it is flagged, and none of its waves reaches a
+                    // barrier (uniform over the workgroup)
+                    // (the wait for the stripe's word only where the launch has such a
+                    // stripe, K.has_empty: it stands in front of the row loads)
+                    if (K.has_empty) {
+                        asm volatile("" : "+s"(vp.first));
+                        if (vp.first == kVerifyNoRow) return;
+                    }
+                }
                 if constexpr (QUAD) issue_quad<L, LR, PK>(A, io, sb, wq, okmq, lane, wave);
                 else issue_rows(kIO{});
                 issue_priv();
@@ -3199,7 +3240,53 @@ hipError_t launch_verify_l(const MonoVerifyArgs &A, hipStream_t s) {
     }
 }
 
+// the same body with a selection per stripe (VMASKS, rs_device.hpp MonoVerifyMaskArgs)
+template <int L, int E>
+__global__ void __launch_bounds__(1 << (L - 1)) k_mono_verify_masks(const MonoVerifyMaskArgs A) {
+    mono_body<L, 1, kMonoEncodeHigh, true, true, false, E, false, false, true>(A);
+}
+
+template <int L, int E>
+hipError_t launch_verify_masks_le(const MonoVerifyMaskArgs &A, hipStream_t s) {
+    constexpr int LR = mono_lr(L, true);
+    static_assert(LR == 1, "k_mono_verify_masks: 2 rows per lane");
+    using G = Stage<L, LR, mono_pk(kMonoEncodeHigh, true, false), E>;
+    size_t lds = size_t(G::words_enc2) * 4;
+    if (E == 2 && lds <= 80 * 1024) lds = 84 * 1024;  // (as launch_ls)
+    static std::atomic<uint64_t> attr_devs{0};
+    if (lds > 65536) {
+        hipError_t e = lds_attr_once(attr_devs, reinterpret_cast<const void *>(&k_mono_verify_masks<L, E>), int(lds));
+        if (e != hipSuccess) return e;
+    }
+    k_mono_verify_masks<L, E><<<dim3(8u * A.packs_per_xcd, A.stripes), 1 << (L - LR), lds, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono_verify_masks<%d, %d>", L, E);
+    return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_verify_masks_l(const MonoVerifyMaskArgs &A, hipStream_t s) {
+    if constexpr (!(RS_MONO_HAS_L(L) && RS_MONO_HAS_MODE(kMonoEncodeHigh) && staged_l(L))) {
+        return hipErrorNotSupported;
+    } else {
+        return A.elems == 2 ? launch_verify_masks_le<L, 2>(A, s) : launch_verify_masks_le<L, 4>(A, s);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_mono_verify_masks(int L, const MonoVerifyMaskArgs &A, hipStream_t s) {
+    if (A.packs == 0 || A.stripes == 0 || A.dst.row_end <= A.dst.row_begin) return hipSuccess;
+    if (!A.flags || !A.sel || !A.first || A.chunks != 1 || A.stripes > 65535 || (A.elems != 2 && A.elems != 4))
+        return hipErrorInvalidValue;
+    switch (L) {
+        case 7: return launch_verify_masks_l<7>(A, s);
+        case 8: return launch_verify_masks_l<8>(A, s);
+        case 9: return launch_verify_masks_l<9>(A, s);
+        case 10: return launch_verify_masks_l<10>(A, s);
+        case 11: return launch_verify_masks_l<11>(A, s);
+        default: return hipErrorNotSupported;
+    }
+}
 
 hipError_t launch_mono_verify(int L, const MonoVerifyArgs &A, hipStream_t s) {
     if (A.packs == 0 || A.stripes == 0 || A.dst.row_end <= A.dst.row_begin) return hipSuccess;

@@ -123,6 +123,10 @@ _sig("rs_verify_set_fused", _int, _vp, _int)
 _sig("rs_locate_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, _vp, _vp, _vp, _E)
 _sig("rs_locate_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, _vp, _vp, _vp, _E)
+_sig("rs_verify_device_batch_masks", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     _vp, _vp, _vp, _E)
+_sig("rs_locate_device_batch_masks", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint8), _vp, _E)
 _sig("rs_locate_device_robust", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p,
      ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_locate_device_robust_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
@@ -1098,6 +1102,7 @@ def update_set_direct_max(k: int, ctx: Optional[Context] = None) -> None:
 
 
 VERIFY_FUSED_DEFAULT = 1  # RS_VERIFY_FUSED_DEFAULT (include/rs_mi355x.h)
+VERIFY_MASKS_FUSED_DEFAULT = 0  # RS_VERIFY_MASKS_FUSED_DEFAULT: verify_device_batch_masks' own default route
 
 
 def _check_flags(d_mismatch, shape, like):
@@ -1164,6 +1169,31 @@ def verify_device_batch(original_count: int, recovery_count: int, shard_bytes: i
     return d_mismatch
 
 
+def verify_device_batch_masks(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                              recovery_rows, d_mismatch=None, stream=None, rate_: int = RATE_DEFAULT,
+                              ctx: Optional[Context] = None):
+    """verify_device on a batch of stripes, each with its OWN row mask (rs_verify_device_batch_masks);
+    tensors [stripes, rows, shard_bytes], recovery_rows a [stripes, recovery_count] array of 0/1.
+    Stripe b ends up as verify_device would leave it with row b of the masks; rows a stripe's mask
+    leaves out are never read in that stripe.  Returns the flag tensor [stripes, recovery_count]."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    rows = _stripe_masks(recovery_rows, n, recovery_count, "recovery_rows")
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_verify_device_batch_masks(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                             d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b,
+                                             rows.ctypes.data, _ptr(d_mismatch), _stream(stream), ctypes.byref(err)),
+           err)
+    return d_mismatch
+
+
 def verify_set_fused(mode: int, ctx: Optional[Context] = None) -> None:
     """0: verify_device always encodes into scratch and compares; 1: the fused column kernel
     where the shape has one (rs_verify_set_fused)."""
@@ -1175,6 +1205,7 @@ def verify_set_fused(mode: int, ctx: Optional[Context] = None) -> None:
 LOCATE_CLEAN = -1    # RS_LOCATE_CLEAN (include/rs_mi355x.h)
 LOCATE_ROWS = -2     # RS_LOCATE_ROWS
 LOCATE_UNKNOWN = -3  # RS_LOCATE_UNKNOWN
+LOCATE_SKIPPED = -4  # RS_LOCATE_SKIPPED (locate_device_batch_masks, status=True)
 
 
 def _check_located(d_located, shape, like):
@@ -1247,6 +1278,50 @@ def locate_device_batch(original_count: int, recovery_count: int, shard_bytes: i
     _raise(_lib.rs_locate_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
                                        d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows,
                                        _ptr(d_located), _ptr(d_mismatch), _stream(stream), ctypes.byref(err)), err)
+    return d_located, d_mismatch
+
+
+def locate_device_batch_masks(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                              recovery_rows, d_located=None, d_mismatch=None, *, status: bool = False, stream=None,
+                              rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """locate_device on a batch of stripes, each with its OWN row mask (rs_locate_device_batch_masks);
+    tensors [stripes, rows, shard_bytes], recovery_rows a [stripes, recovery_count] array of 0/1.
+    Returns (located [stripes], mismatch [stripes, recovery_count]) as locate_device_batch does.
+
+    status=False: a stripe whose mask selects fewer than two rows raises ValueError with that stripe's
+    number in the attribute `stripe`; nothing has been written then.
+    status=True: returns (located, mismatch, codes), codes a numpy uint8 array of one rs_status per
+    stripe (0 = ok, 101 = fewer than two rows selected: that stripe is skipped -- none of its rows
+    read, flags 0, located LOCATE_SKIPPED -- and the others are located)."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    if recovery_count < 2:
+        raise ValueError("recovery_rows: a locate needs two recovery rows at least (verify_device takes fewer)")
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    rows = _stripe_masks(recovery_rows, n, recovery_count, "recovery_rows")
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    codes = (ctypes.c_uint8 * n)() if status else None
+    err = _RsError()
+    code = _lib.rs_locate_device_batch_masks(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                             d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b,
+                                             rows.ctypes.data, _ptr(d_located), _ptr(d_mismatch), codes,
+                                             _stream(stream), ctypes.byref(err))
+    if code == 101 and not status and n and int(rows.sum(axis=1).min()) < 2:
+        e = ValueError(f"recovery_rows: stripe {int(err.index)} selects fewer than two rows "
+                       "(a locate needs two; status=True skips such stripes)")
+        e.stripe = int(err.index)
+        raise e
+    _raise(code, err)
+    if status:
+        import numpy as np
+
+        return d_located, d_mismatch, np.frombuffer(codes, dtype=np.uint8).copy()
     return d_located, d_mismatch
 
 
