@@ -42,7 +42,8 @@
  *   original of a stripe whose recovery shards all disagree
  *   rs_locate_device_robust (+ _batch): the locate that tolerates, and names, a
  *   few corrupt recovery shards beside the corrupt original
- *   rs_heal_device (+ _batch): the locate that also writes the correction, to the
+ *   rs_heal_device (+ _batch; rs_heal_device_batch_masks: a recovery-row mask
+ *   per stripe): the locate that also writes the correction, to the
  *   located original or to the differing recovery rows, with no host round trip
  *
  * Thread-safety: a context may be shared by threads (like DefaultEngine:
@@ -766,8 +767,8 @@ rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
  * covers the largest count).
  *   Measured (tools/verify_masks_time.py, profiles/verify_masks/): see DESIGN.md
  * §4.4k.
- *   Not covered: per-stripe masks for rs_heal_device*, the robust and the degraded
- * calls; a fused form on k_mono_verify_masks; the host pipeline, the object API
+ *   Not covered: per-stripe masks for the robust and the degraded calls (the heal
+ * has them: rs_heal_device_batch_masks below); a fused form on k_mono_verify_masks; the host pipeline, the object API
  * and the sharded classes. */
 #define RS_LOCATE_SKIPPED (-4)
 rs_status rs_locate_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t original_count,
@@ -1122,7 +1123,9 @@ rs_status rs_locate_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_
  * the masks.  DESIGN.md "Heal" has the rest.
  *   Not covered: a mask per stripe; stripes with missing originals
  * (rs_locate_device_degraded above locates in those); the host
- * pipeline, the object API and the sharded classes. */
+ * pipeline, the object API and the sharded classes.  (The mask per stripe is not
+ * covered by these two calls: rs_heal_device_batch_masks below takes one.  The
+ * robust and the degraded heal have no such form.) */
 #define RS_HEAL_ORIGINAL 1u /* a located original i: original_i ^= e */
 #define RS_HEAL_RECOVERY 2u /* a ROWS stripe: rewrite its differing selected rows */
 rs_status rs_heal_device(rs_context *ctx, rs_rate rate, uint64_t original_count, uint64_t recovery_count,
@@ -1135,6 +1138,94 @@ rs_status rs_heal_device_batch(rs_context *ctx, rs_rate rate, uint64_t original_
                                uint64_t recovery_stripe_stride, const uint8_t *recovery_check, uint32_t mode,
                                uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action,
                                void *stream, rs_error *err);
+
+/* ---- heal with a mask per stripe ----
+ * rs_heal_device_batch with the per-stripe masks of rs_locate_device_batch_masks:
+ * recovery_check is a HOST array of stripes x recovery_count bytes of 0/1,
+ * stripe-major, NOT NULL; it is copied through the stream's staging and may be
+ * reused or freed when the call returns.  Everything else -- matrices, strides,
+ * mode, max_rows, the three outputs, the table -- is the heal's.
+ *   Stripe b ends exactly as if rs_heal_device had been called on it with row b of
+ * the mask and the same mode and max_rows: d_located and d_mismatch describe the
+ * stripe as found and equal what rs_locate_device_batch_masks writes; d_action[b]
+ * and both matrices are as rs_heal_device leaves them (e comes from the STRIPE's
+ * first selected row); max_rows is compared with the stripe's own count of
+ * differing selected rows.  A row that stripe b's mask does not select is never read
+ * and never written in that stripe.  Every byte of d_mismatch and d_action and every
+ * word of d_located is defined after the call; row padding, stripe padding and
+ * anything else are untouched.  The CAVEAT of rs_heal_device about RS_HEAL_RECOVERY
+ * holds here unchanged.
+ *   Errors, all before any device work, in this order: null context, d_original,
+ * d_recovery, d_located, d_mismatch, d_action or recovery_check ->
+ * RS_ERR_INVALID_ARGUMENT; rs_validate; the two row strides; mode == 0 or a bit
+ * outside the two -> RS_ERR_INVALID_ARGUMENT; stripes == 0: RS_OK, nothing touched;
+ * recovery_count < need (need = 3 with RS_HEAL_ORIGINAL, else 2: the heal's own
+ * rule), original_count > RS_LOCATE_MAX_ORIGINALS or original_count x recovery_count
+ * > RS_LOCATE_MAX_COEFFICIENTS -> RS_ERR_INVALID_ARGUMENT.  Then every stripe's mask
+ * is counted on the host, in stripe order.  A stripe that selects fewer than `need`
+ * rows cannot be healed, and
+ *   stripe_status == NULL: the call is all or nothing.  RS_ERR_INVALID_ARGUMENT with
+ *     the first such stripe's number in err->index; nothing is launched, nothing
+ *     is written, the context is not touched.
+ *   stripe_status != NULL (HOST, `stripes` bytes): every stripe gets one rs_status,
+ *     RS_OK or RS_ERR_INVALID_ARGUMENT.  A stripe that cannot be healed is skipped:
+ *     none of its memory is read or written, its flags are all 0, d_located[b] =
+ *     RS_LOCATE_SKIPPED and d_action[b] = 0.  The others are healed and the call
+ *     returns RS_OK.
+ * The matrices must not overlap one another or the three outputs.
+ *   The table is the plain locate's and is shared every way: a stream warm from
+ * rs_locate_device*, rs_heal_device* or this call builds none for any of the others.
+ *   Launches, per 65535 stripes where the batch encode is one launch, else per
+ * stripe: those of rs_locate_device_batch_masks (k_locate_find_masks also stores
+ * the stripe's count of differing rows into per-stream scratch), then one
+ * k_heal_masks directly after the group's k_locate_confirm_masks, while the group's
+ * encode is still in scratch.  k_heal_masks has the confirm's grid; block (0, 0, b)
+ * stores d_action[b], and the workgroups of a stripe with nothing to heal leave at
+ * once.  A group in which no stripe can be healed has no confirm and no
+ * k_heal_masks: where the batch has such a group, d_action is zeroed by a memset at
+ * the start of the call, beside the flags' memset, and that zero is those stripes'
+ * action (no heal launch; a batch without such a group has no memset of d_action,
+ * since every k_heal_masks stores all the action bytes of its group).
+ *   Measured (tools/heal_masks_time.py, profiles/heal_masks/heal_masks_time.txt;
+ * 1024:1024, a random 10 % of every stripe's rows unselected, both mode bits,
+ * max_rows 16, us per call, median of 5 rounds of 50 back-to-back calls, the legs
+ * interleaved in one session; locate = rs_locate_device_batch_masks on the same
+ * batch, spread = max - min of its five rounds; "parent" = that leg on the parent
+ * commit's build in the same session, the yardstick; original / row = one corrupt
+ * original / one corrupt selected row in EVERY stripe, net of the 5.0-5.7 us
+ * launch that puts the damage back, and in brackets what the leg adds over the
+ * clean locate beside what rs_heal_device_batch's leg adds over
+ * rs_locate_device_batch; singles = one rs_heal_device per stripe):
+ *     shape               parent spread  locate spread  heal clean  heal original         heal row            singles
+ *     1 KiB, 64 stripes   259.24   1.15  259.83   4.53  262.27      288.88 (+29.1 | +28.8)  263.28 (+3.5 | +4.8)  1537.2
+ *     64 KiB, one stripe  133.85   2.96  134.04   1.29  138.08      174.26 (+40.2 | +40.5)  141.09 (+7.1 | +4.4)   128.3
+ * The expectation was: a clean batch costs the locate plus one small launch, i.e.
+ * lies within the locate leg's spread plus one launch floor -- an empty-work k_heal
+ * between two of the library's events, 6.2 us at both shapes in this session
+ * (k_heal_masks 6.1 us at 64 stripes; 10.0 us in the one profiled clean call at
+ * 64 KiB, 6.2 us in the next).  Met: +3.0 and +4.2 us over the parent's locate
+ * (+2.4 and +4.0 over this build's).  The locate leg itself is +0.6 and +0.2 us
+ * from the parent's, inside its own spread: the one optional store costs nothing
+ * that shows.  A corrupt original adds what the shared-mask heal's adds, within
+ * 0.3 us.  A corrupt row adds 1.4 us LESS than the shared-mask heal's at 64
+ * stripes and 2.7 us MORE at 64 KiB, where the legs spread 0.4-1.3 us: that one is
+ * outside the expectation, and the cause was not isolated (the clean call already
+ * stands 2.1 us further above its locate than rs_heal_device_batch does above
+ * its own; k_heal_masks' copy, 9.3 us, is k_heal's).  Against the 64-call loop of
+ * rs_heal_device the call is 5.9 times cheaper; against rs_heal_device_batch with
+ * every row selected it is 1.12 / 1.07 times dearer, which is the masks locate's
+ * own distance from the plain locate (the staging copy of the row lists).
+ * DESIGN.md §4.4l has the rest.
+ *   Not covered: per-stripe masks for the robust and the degraded heal; a fused
+ * form on k_mono_verify_masks; the host pipeline, the object API and the sharded
+ * classes. */
+rs_status rs_heal_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                     uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                     void *d_original, uint64_t original_stride, uint64_t original_stripe_stride,
+                                     void *d_recovery, uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                     const uint8_t *recovery_check, uint32_t mode, uint32_t max_rows,
+                                     int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action,
+                                     uint8_t *stripe_status, void *stream, rs_error *err);
 
 /* ---- robust heal: heal the original and its outlier rows, in place ----
  * rs_heal_device is built on the plain locate, so one rotten original plus a

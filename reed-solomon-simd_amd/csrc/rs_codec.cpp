@@ -2238,10 +2238,13 @@ void verify_masks_fused(rs_context *ctx, Workspace &ws, bool high, Geom g, const
 // group when no stripe is left alone), then one compare per run, and one find and one
 // confirm for the group; elsewhere stripe by stripe, each with its own span, and a
 // stripe with sel[b].nsel = 0 costs no encode and no compare.  The caller has zeroed
-// the flags.
+// the flags.  With a heal (rs_heal_device_batch_masks) k_heal_masks is a
+// third launch per group, straight after the group's confirm and while its encode is
+// still in scratch; a group in which every stripe is skipped has neither, so the caller
+// has zeroed d_action as well.
 void masks_unfused(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const VerifyCall &V,
                    const std::vector<StripeSel> &sel, bool column, int32_t *d_located, const uint16_t *logs,
-                   hipStream_t s) {
+                   hipStream_t s, const HealCall *H = nullptr) {
     const uint32_t M = uint32_t(V.M);
     if (!ws.ver) ws.ver.reset(new VerifyWs);
     VerifyWs &v = *ws.ver;
@@ -2269,6 +2272,8 @@ void masks_unfused(rs_context *ctx, Workspace &ws, bool high, const Geom &g, con
     ge.rec_stride = W;
     ge.orig_bstride = V.orig_bstride;
     ge.rec_bstride = V.M * W;
+    uint32_t *differ = nullptr;  // (the caller's locate_table has made ws.loc)
+    if (H) differ = static_cast<uint32_t *>(ws.loc->differ.get(std::min<uint64_t>(group, V.stripes) * 4));
     for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
         const uint64_t b1 = b0 + std::min<uint64_t>(group, V.stripes - b0);
         // the encode and the compare over every run of consecutive stripes that select
@@ -2297,7 +2302,7 @@ void masks_unfused(rs_context *ctx, Workspace &ws, bool high, const Geom &g, con
         if (!d_located) continue;
         // one find and one confirm for the group, as the plain locate's
         const StripeSel u = union_sel(sel, b0, b1, M);
-        rs::LocateMaskArgs A;
+        rs::HealMaskArgs A;  // the locate's kernels take its LocateMaskArgs
         A.want = enc, A.want_stride = W, A.want_bstride = V.M * W;
         A.have = V.d_rec + b0 * V.rec_bstride, A.have_stride = g.rec(), A.have_bstride = V.rec_bstride;
         A.rows = d_lists + b0 * M, A.list_stride = M, A.counts = d_counts + b0;
@@ -2307,10 +2312,18 @@ void masks_unfused(rs_context *ctx, Workspace &ws, bool high, const Geom &g, con
         A.located = d_located + b0;
         A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
         A.fmt = g.fmt;
+        A.differ = differ;
         update_launch(s, (V.M + 4) * uint64_t(A.stripes), [&] { return rs::launch_locate_find_masks(A, s); });
-        if (u.nsel >= 2)
-            update_launch(s, 2 * uint64_t(u.nsel) * pack_bytes * A.stripes,
-                          [&] { return rs::launch_locate_confirm_masks(A, s); });
+        if (u.nsel < 2) continue;  // every stripe of the group is skipped (a heal's d_action: the caller's memset)
+        update_launch(s, 2 * uint64_t(u.nsel) * pack_bytes * A.stripes,
+                      [&] { return rs::launch_locate_confirm_masks(A, s); });
+        if (!H) continue;
+        A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
+        A.rec = H->d_rec + b0 * V.rec_bstride;
+        A.mode = H->mode, A.max_rows = H->max_rows;
+        A.action = H->d_action + b0;
+        // as locate_dev's k_heal: a stripe with nothing to heal costs a word
+        update_launch(s, 5 * uint64_t(A.stripes), [&] { return rs::launch_heal_masks(A, s); });
     }
 }
 
@@ -3983,6 +3996,67 @@ rs_status rs_heal_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, 
                          void *stream, rs_error *err) {
     return rs_heal_device_batch(ctx, rate, N, M, S, 1, d_orig, orig_stride, 0, d_rec, rec_stride, 0, recovery_check,
                                 mode, max_rows, d_located, d_mismatch, d_action, stream, err);
+}
+
+rs_status rs_heal_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                     uint64_t stripes, void *d_orig, uint64_t orig_stride,
+                                     uint64_t orig_stripe_stride, void *d_rec, uint64_t rec_stride,
+                                     uint64_t rec_stripe_stride, const uint8_t *recovery_check, uint32_t mode,
+                                     uint32_t max_rows, int32_t *d_located, uint8_t *d_mismatch, uint8_t *d_action,
+                                     uint8_t *stripe_status, void *stream, rs_error *err) {
+    if (!ctx || !ptr_ok(d_orig) || !ptr_ok(d_rec) || !ptr_ok(d_located) || !ptr_ok(d_mismatch) || !ptr_ok(d_action) ||
+        !recovery_check)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0) return set_err(err, RS_OK);
+    // the heal's own rule (rs_heal_device_batch), stripe by stripe
+    const uint32_t need = (mode & RS_HEAL_ORIGINAL) ? 3u : 2u;
+    if (M < need || N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS)
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    return guarded(err, [&]() -> rs_status {
+        // every stripe's mask, in stripe order, before any device work
+        std::vector<StripeSel> sel(stripes);
+        for (uint64_t b = 0; b < stripes; ++b) {
+            sel[b] = stripe_sel(recovery_check + b * M, uint32_t(M));
+            if (stripe_status) stripe_status[b] = sel[b].nsel < need ? RS_ERR_INVALID_ARGUMENT : RS_OK;
+            if (sel[b].nsel >= need) continue;
+            if (!stripe_status) {
+                set_err(err, RS_ERR_INVALID_ARGUMENT);
+                if (err) err->index = b;
+                return RS_ERR_INVALID_ARGUMENT;
+            }
+            sel[b] = StripeSel{uint32_t(M), 0, 0};  // skipped: none of its rows is read or written
+        }
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
+        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
+                     0, 0, recovery_check, d_mismatch};
+        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
+            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        const uint16_t *logs = locate_table(ctx, sw.w, high != 0, N, M, s);
+        check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
+        uint32_t L = 0;
+        const bool column = verify_column(ctx, high != 0, g, N, M, &L);
+        // a group whose stripes are all skipped launches no k_heal_masks: their action is this
+        // zero.  (Every other group's launch stores all of its action bytes: a batch without
+        // such a group pays for no memset.)
+        bool idle = false;
+        for (uint64_t b0 = 0, group = column ? kMaxBatchStripes : 1; b0 < stripes && !idle; b0 += group)
+            idle = !union_sel(sel, b0, std::min<uint64_t>(b0 + group, stripes), uint32_t(M)).nsel;
+        if (idle) check(hipMemsetAsync(d_action, 0, stripes, s));
+        masks_unfused(ctx, sw.w, high != 0, g, V, sel, column, d_located, logs, s, &H);
+        return set_err(err, RS_OK);
+    });
 }
 
 // ---- robust heal: the robust locate that also writes the correction (include/rs_mi355x.h) ----

@@ -602,6 +602,20 @@ struct HealArgs : LocateArgs {
     uint8_t *action = nullptr;  // one byte per stripe
 };
 hipError_t launch_heal(const HealArgs &A, hipStream_t stream);
+// launch_heal with one row list PER STRIPE (k_heal_masks; rs_heal_device_batch_masks,
+// DESIGN.md §4.4l), after launch_locate_find_masks (with `differ`) and
+// launch_locate_confirm_masks of the same arguments, on the latter's grid: the row
+// whose D gives e is the stripe's own rows[b * list_stride], and a kLocateRows stripe
+// walks its own counts[b] entries.  A skipped stripe gets action[b] = 0 and nothing of
+// it is read.  Derived from LocateMaskArgs, so that the three *_masks launches of a
+// group take one object; the heal's fields are HealArgs'.
+struct HealMaskArgs : LocateMaskArgs {
+    uint8_t *orig = nullptr, *rec = nullptr;
+    uint64_t orig_stride = 0, orig_bstride = 0;
+    uint32_t mode = 0, max_rows = 0;
+    uint8_t *action = nullptr;  // one byte per stripe
+};
+hipError_t launch_heal_masks(const HealMaskArgs &A, hipStream_t stream);
 
 // ---- degraded heal (rs_heal_device_degraded*, rs_locate.hip; DESIGN.md "Degraded heal") ----
 // launch_locate_log_rows is launch_locate_log over a row list: logs[r * pitch + i0 + c]

@@ -26,6 +26,9 @@
 //                      confirm's e, recomputed); a ROWS stripe within the caller's
 //                      threshold: its flagged selected rows copied from the scratch;
 //                      one action byte per stripe
+//   k_heal_masks       k_heal with a row list and a count per stripe
+//                      (rs_heal_device_batch_masks), after the two
+//                      *_masks kernels above; a skipped stripe costs its action byte
 //
 // and of a degraded locate (rs_locate_device_degraded*, DESIGN.md "Degraded locate"),
 // whose `want` is the repair's second output and whose table is over information
@@ -262,6 +265,7 @@ __global__ __launch_bounds__(kFindThreads) void k_locate_find_masks(const Locate
     if (c) atomicAdd(&s_count, c);
     __syncthreads();
     const uint32_t differ = s_count;
+    if (A.differ && tid == 0) A.differ[b] = differ;
     if (differ < nsel) {
         if (tid == 0) A.located[b] = differ ? kLocateRows : kLocateClean;
         return;
@@ -380,6 +384,54 @@ __global__ __launch_bounds__(256) void k_heal(const HealArgs A) {
     const uint32_t r1 = r0 + A.rows_per_group < A.nsel ? r0 + A.rows_per_group : A.nsel;
     for (uint32_t r = r0; r < r1; ++r) {
         const uint32_t j = A.rows ? rows[r] : r;
+        if (!__builtin_amdgcn_readfirstlane(uint32_t(flags[j])) || !ok) continue;
+        const uint8_t *w = want + uint64_t(j) * A.want_stride + io.lo;
+        uint8_t *h = rec + uint64_t(j) * A.have_stride + io.lo;
+        st_word(h, ld_word(w, io), io);
+        st_word(h + io.hi_delta, ld_word(w + io.hi_delta, io), io);
+    }
+}
+
+// k_heal with stripe b's own row list and count (rs_device.hpp HealMaskArgs), on the grid
+// of k_locate_confirm_masks: j0 is the STRIPE's first selected row, and a row group at or
+// past the stripe's count has no row.  A skipped stripe (located[b] = kLocateSkipped)
+// costs its action byte and nothing else: its flags, differ[b], rows and matrices are
+// never read.
+__global__ __launch_bounds__(256) void k_heal_masks(const HealMaskArgs A) {
+    const uint64_t b = blockIdx.z;
+    const int32_t loc = __builtin_amdgcn_readfirstlane(A.located[b]);
+    uint32_t action = 0;
+    if (loc >= 0) {
+        if (A.mode & kHealOriginal) action = kHealOriginal;
+    } else if (loc == kLocateRows && (A.mode & kHealRecovery)) {
+        if (uint32_t(__builtin_amdgcn_readfirstlane(A.differ[b])) <= A.max_rows) action = kHealRecovery;
+    }
+    if ((blockIdx.x | blockIdx.y | threadIdx.x) == 0) A.action[b] = uint8_t(action);
+    if (!action) return;
+    const uint32_t pk = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = pk < A.packs;
+    const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
+    const uint8_t *want = A.want + b * A.want_bstride;
+    const ConstWords rows = const_words(A.rows + b * A.list_stride);
+    if (action == kHealOriginal) {
+        if (blockIdx.y) return;  // one row to write: row group 0 does it
+        uint32_t el, eh;
+        locate_error(A, const_words(A.logs), const_words(A.lut), rows[0], uint32_t(loc), want,
+                     A.have + b * A.have_bstride, io, ok, el, eh);
+        if (!ok) return;
+        uint8_t *p = A.orig + b * A.orig_bstride + uint64_t(loc) * A.orig_stride + io.lo;
+        st_word(p, ld_word(p, io) ^ el, io);
+        st_word(p + io.hi_delta, ld_word(p + io.hi_delta, io) ^ eh, io);
+        return;
+    }
+    const uint32_t nsel = const_words(A.counts)[b];
+    const uint32_t r0 = blockIdx.y * A.rows_per_group;
+    const uint32_t r1 = r0 + A.rows_per_group < nsel ? r0 + A.rows_per_group : nsel;
+    if (r0 >= r1) return;
+    const uint8_t *flags = A.flags + b * A.flag_bstride;
+    uint8_t *rec = A.rec + b * A.have_bstride;
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t j = rows[r];
         if (!__builtin_amdgcn_readfirstlane(uint32_t(flags[j])) || !ok) continue;
         const uint8_t *w = want + uint64_t(j) * A.want_stride + io.lo;
         uint8_t *h = rec + uint64_t(j) * A.have_stride + io.lo;
@@ -570,6 +622,23 @@ hipError_t launch_heal(const HealArgs &A0, hipStream_t s) {
     if (grid.y > 65535) return hipErrorInvalidValue;
     k_heal<<<grid, threads, 0, s>>>(A);
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_heal");
+    return hipGetLastError();
+}
+
+hipError_t launch_heal_masks(const HealMaskArgs &A0, hipStream_t s) {
+    if (!A0.stripes) return hipSuccess;
+    if (!A0.rows || !A0.counts || A0.nsel < 2 || !A0.packs || A0.stripes > 65535 || !A0.differ || !A0.action ||
+        !A0.orig || !A0.rec || !A0.mode || (A0.mode & ~(kHealOriginal | kHealRecovery)))
+        return hipErrorInvalidValue;
+    HealMaskArgs A = A0;
+    // the confirm's grid (launch_locate_confirm_masks) over the largest count
+    const uint32_t threads = A.packs >= 256 ? 256u : (A.packs + 63u) / 64u * 64u, tiles = (A.packs + threads - 1) / threads;
+    const uint64_t units = uint64_t(A.nsel) * tiles * A.stripes;
+    A.rows_per_group = uint32_t(units / 1024 < 1 ? 1 : units / 1024 > 16 ? 16 : units / 1024);
+    const dim3 grid(tiles, (A.nsel + A.rows_per_group - 1) / A.rows_per_group, A.stripes);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    k_heal_masks<<<grid, threads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_heal_masks");
     return hipGetLastError();
 }
 

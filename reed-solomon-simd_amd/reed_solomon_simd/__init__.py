@@ -139,6 +139,8 @@ _sig("rs_heal_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, 
      ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
 _sig("rs_heal_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
      ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _E)
+_sig("rs_heal_device_batch_masks", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
+     _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint8), _vp, _E)
 _sig("rs_heal_device_robust", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p,
      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _E)
 _sig("rs_heal_device_robust_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
@@ -1575,6 +1577,60 @@ def heal_device_batch(original_count: int, recovery_count: int, shard_bytes: int
                                      d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b, rows, mode,
                                      max_rows, _ptr(d_located), _ptr(d_mismatch), _ptr(d_action), _stream(stream),
                                      ctypes.byref(err)), err)
+    return d_located, d_mismatch, d_action
+
+
+def heal_device_batch_masks(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
+                            recovery_rows, mode: int = HEAL_ORIGINAL, max_rows: int = 0, d_located=None,
+                            d_mismatch=None, d_action=None, *, status: bool = False, stream=None,
+                            rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None):
+    """heal_device on a batch of stripes, each with its OWN row mask (rs_heal_device_batch_masks);
+    tensors [stripes, rows, shard_bytes], recovery_rows a [stripes, recovery_count] array of 0/1.
+    Returns (located [stripes], mismatch [stripes, recovery_count], action [stripes]) as
+    heal_device_batch does; max_rows is compared with each stripe's own count of differing rows.
+
+    A stripe needs three selected rows with HEAL_ORIGINAL in `mode`, else two.
+    status=False: a stripe whose mask selects fewer raises ValueError with that stripe's number in
+    the attribute `stripe`; nothing has been written then.
+    status=True: returns (located, mismatch, action, codes), codes a numpy uint8 array of one
+    rs_status per stripe (0 = ok, 101 = too few rows selected: that stripe is skipped -- none of its
+    memory read or written, flags 0, located LOCATE_SKIPPED, action 0 -- and the others are healed)."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    mode, max_rows = int(mode), int(max_rows)
+    if mode == 0 or mode & ~(HEAL_ORIGINAL | HEAL_RECOVERY):
+        raise ValueError(f"mode: HEAL_ORIGINAL | HEAL_RECOVERY, at least one (locate_device takes none), got {mode}")
+    if not 0 <= max_rows < 1 << 32:
+        raise ValueError(f"max_rows: 0 .. 2^32 - 1, got {max_rows}")
+    need = 3 if mode & HEAL_ORIGINAL else 2
+    if recovery_count < need:
+        raise ValueError(f"recovery_rows: this heal needs {need} recovery rows at least (three with HEAL_ORIGINAL)")
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    rows = _stripe_masks(recovery_rows, n, recovery_count, "recovery_rows")
+    d_located = _check_located(d_located, (n,), d_recovery)
+    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_action = _check_action(d_action, (n,), d_recovery)
+    (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
+    codes = (ctypes.c_uint8 * n)() if status else None
+    err = _RsError()
+    code = _lib.rs_heal_device_batch_masks(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                           d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b,
+                                           rows.ctypes.data, mode, max_rows, _ptr(d_located), _ptr(d_mismatch),
+                                           _ptr(d_action), codes, _stream(stream), ctypes.byref(err))
+    if code == 101 and not status and n and int(rows.sum(axis=1).min()) < need:
+        e = ValueError(f"recovery_rows: stripe {int(err.index)} selects fewer than {need} rows "
+                       "(three with HEAL_ORIGINAL, else two; status=True skips such stripes)")
+        e.stripe = int(err.index)
+        raise e
+    _raise(code, err)
+    if status:
+        import numpy as np
+
+        return d_located, d_mismatch, d_action, np.frombuffer(codes, dtype=np.uint8).copy()
     return d_located, d_mismatch, d_action
 
 
