@@ -12,6 +12,7 @@ import locate_model as LM
 import locate_robust_model as RM
 import oracle_lib as O
 import test_gpu_verify as V
+import wide_cases as W
 from test_gpu_locate import damage_original
 
 CLEAN, ROWS, UNKNOWN = LM.CLEAN, LM.ROWS, LM.UNKNOWN
@@ -45,9 +46,50 @@ def hit(rec, j, kind, form):
         rec[j, S - 1 if form == "bit0" else 0] ^= 0x40
 
 
-def cases(rate, N, M, S, mask=None, forms=("bit0", "lastbit"), ts=None, junk=False):
+def wide_cases(rate, N, M, S):
+    """The positional cases of a wide shard (tests/wide_cases.py), at t = 1 and 2, every row
+    selected: clean; original N // 2 corrupt as a whole shard with t outlier rows whose only damage is
+    in the last pack; original 0 corrupt in pack 0 alone with an outlier row damaged in the last pack,
+    a column where e = 0; the whole shard again with t + 1 outliers, one in each of the first t + 1
+    pairs, damaged in the last pack: UNKNOWN."""
+    orig, rec = V.stripe(rate, N, M, S)
+    packs = W.packs_of(S)
+    rng = np.random.default_rng(N * 7 + M + S)
+    out = [("none", 1, orig, rec, encoded((rate, N, M, S, "clean"), orig, rate, M), (CLEAN, []))]
+    shard = orig.copy()
+    shard[N // 2] ^= rng.integers(1, 256, S, dtype=np.uint8)
+    shard_enc = encoded((rate, N, M, S, "wide shard"), shard, rate, M)
+    narrow = orig.copy()
+    W.damage_pack(narrow, 0, 0, rng)
+    narrow_enc = encoded((rate, N, M, S, "wide pack 0"), narrow, rate, M)
+    assert M >= 2 * 2 + 3
+
+    def hit_rows(rows):
+        r = rec.copy()
+        for j in rows:
+            W.damage_pack(r, j, packs - 1, rng)
+        return r
+
+    for t in (1, 2):
+        rows = [0, M - 1][:t] if t == 1 else [1, M // 2]
+        out.append((f"original {N // 2} shard, outliers {rows} pack {packs - 1} t={t}", t, shard, hit_rows(rows),
+                    shard_enc, (N // 2, rows)))
+        rows = [M // 2] if t == 1 else [0, M - 1]
+        out.append((f"original 0 pack 0, ezero outliers {rows} pack {packs - 1} t={t}", t, narrow, hit_rows(rows),
+                    narrow_enc, (0, rows)))
+        rows = [2 * p + (p & 1) for p in range(t + 1)]
+        out.append((f"original {N // 2} shard, {t + 1} outliers pack {packs - 1} t={t}", t, shard, hit_rows(rows),
+                    shard_enc, (UNKNOWN, [])))
+    return out
+
+
+def cases(rate, N, M, S, mask=None, forms=("bit0", "lastbit"), ts=None, junk=False, wide=False):
     """Every case of the issue that the shape has rows for.  ts: the values of t the outlier cases
-    run at (default 1, 2 and the largest allowed); junk: 0xC3 in the unselected rows."""
+    run at (default 1, 2 and the largest allowed); junk: 0xC3 in the unselected rows; wide:
+    wide_cases' instead."""
+    if wide:
+        assert mask is None
+        return wide_cases(rate, N, M, S)
     orig, rec = V.stripe(rate, N, M, S)
     sel = np.arange(M) if mask is None else np.flatnonzero(np.asarray(mask) != 0)
     c, top = len(sel), t_max(len(sel))

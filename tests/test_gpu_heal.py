@@ -17,6 +17,7 @@ import locate_model as LM
 import oracle_lib as O
 import test_gpu_locate as L
 import test_gpu_verify as V
+import wide_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -125,9 +126,11 @@ def heal_one(torch, rs, rate, N, M, S, orig, rec, pad=0, mask=None, mode=3, max_
     return w_loc, w_flags, w_act, w_orig, w_rec
 
 
-def run_cases(torch, rs, rate, N, M, S, pad=0, mode=3, only=None):
+def run_cases(torch, rs, rate, N, M, S, pad=0, mode=3, only=None, wide=False, again=False):
+    """wide: the positional cases of tests/wide_cases.py; again: every stripe the heal wrote is healed
+    a second time from what the first heal left, which must be CLEAN with action 0."""
     clean_orig, clean_rec = V.stripe(rate, N, M, S)
-    for name, orig, rec, intended in L.cases(rate, N, M, S):
+    for name, orig, rec, intended in L.cases(rate, N, M, S, wide):
         if only and not any(name.startswith(o) for o in only):
             continue
         what = f"{rate} {N}:{M} x {S} pad {pad} mode {mode} {name}"
@@ -143,6 +146,10 @@ def run_cases(torch, rs, rate, N, M, S, pad=0, mode=3, only=None):
             assert np.array_equal(o2, orig), what
         elif loc in (UNKNOWN, CLEAN):
             assert act == 0 and np.array_equal(o2, orig) and np.array_equal(r2, rec), what
+        if again and act:
+            loc, flags, act, _, _ = heal_one(torch, rs, rate, N, M, S, o2, r2, pad, mode=mode, max_rows=M - 1,
+                                             what=what + ", healed again")
+            assert (loc, act) == (CLEAN, 0) and not flags.any(), f"{what}: a second heal gives {loc}, action {act}"
 
 
 @pytest.mark.parametrize("S,pad", LAYOUTS, ids=lambda v: str(v))
@@ -250,8 +257,10 @@ def test_masks(torch, rs, rate, N, M, S, pad):
         assert (loc, act) == (UNKNOWN, 0) and np.array_equal(r2, worse)
 
 
-def batch_case(rate, N, M, S, B, max_rows):
-    """B stripes with a different outcome in each: [originals], [recovery], [intended status]."""
+def batch_case(rate, N, M, S, B, max_rows, wide=False):
+    """B stripes with a different outcome in each: [originals], [recovery], [intended status].
+    wide: recovery rows are damaged in the last pack, the middle pack and pack 0
+    (tests/wide_cases.py), not all in the first block."""
     rng = np.random.default_rng(B)
     kinds = ["orig0", "clean", "row", "origN", "over", "unknown", "rows", "origmid"][:B]
     origs, recs, wants = [], [], []
@@ -262,8 +271,12 @@ def batch_case(rate, N, M, S, B, max_rows):
             want = {"orig0": 0, "origN": N - 1, "origmid": N // 2}[k]
             L.damage_original(o, want, {"orig0": "lastbit", "origN": "shard", "origmid": "highhalf"}[k], rng)
         elif k in ("row", "rows", "over"):
+            packs = W.packs_of(S)
             for n, j in enumerate([M - 1, 0, M // 2][:{"row": 1, "rows": max_rows, "over": max_rows + 1}[k]]):
-                r[j, (3 + 7 * n) % S] ^= 0x02 << n
+                if wide:
+                    W.damage_pack(r, j, [packs - 1, packs // 2, 0][n], rng)
+                else:
+                    r[j, (3 + 7 * n) % S] ^= 0x02 << n
             want = ROWS
         elif k == "unknown":
             o[0, 0] ^= 0x10
@@ -276,13 +289,15 @@ def batch_case(rate, N, M, S, B, max_rows):
 @pytest.mark.parametrize("rate,N,M,S,B,pad", [("high", 70, 100, 66, 8, 4), ("default", 1024, 1024, 72, 6, 0),
                                               ("high", 1000, 100, 66, 5, 0), ("low", 128, 1024, 64, 4, 0),
                                               ("default", 4096, 4096, 64, 4, 0)], ids=lambda v: str(v))
-def test_batch(torch, rs, rate, N, M, S, B, pad):
+def test_batch(torch, rs, rate, N, M, S, B, pad, wide=False, groups=None):
     """A different outcome in every stripe, with stripe padding.  One launch of each kernel where
     the batch encode is one launch; stripe by stripe elsewhere, which is the case that catches a
     k_heal reading another stripe's scratch.  Byte-identical to the model, to a loop of single
-    calls, and healed a second time: CLEAN, action 0, nothing written."""
+    calls, and healed a second time: CLEAN, action 0, nothing written.  (wide, groups:
+    tests/test_gpu_wide_shards.py's -- batch_case's wide form, and the number of groups the batch
+    must run in where the shape alone does not say.)"""
     max_rows = 2
-    origs, recs, intended = batch_case(rate, N, M, S, B, max_rows)
+    origs, recs, intended = batch_case(rate, N, M, S, B, max_rows, wide)
     model = [HM.heal(rate, origs[b], recs[b], mode=3, max_rows=max_rows) for b in range(B)]
     assert [m[0] for m in model] == intended
     w_orig, w_rec = np.stack([m[3] for m in model]), np.stack([m[4] for m in model])
@@ -304,8 +319,8 @@ def test_batch(torch, rs, rate, N, M, S, B, pad):
     d_orig.check(w_orig, "batch: d_original")
     d_rec.check(w_rec, "batch: d_recovery")
     # the launches: the locate's list plus exactly one k_heal per group, after its confirm
-    groups = names.count("k_locate_confirm")
-    assert groups == {70: 1, 1024: 1}.get(N, B), names
+    want_groups, groups = groups, names.count("k_locate_confirm")
+    assert groups == ({70: 1, 1024: 1}.get(N, B) if want_groups is None else want_groups), names
     assert names.count("k_heal") == groups == names.count("k_locate_find") == names.count("k_verify_rows"), names
     assert all(names[k + 1] == "k_heal" for k, n in enumerate(names) if n == "k_locate_confirm"), names
     plain = [r[0] for r in V.profiled(torch, rs, locate)]

@@ -69,9 +69,12 @@ def pattern(kind, N, M):
     return present, mask
 
 
-def cases(rate, N, M, S, present, mask):
+def cases(rate, N, M, S, present, mask, wide=False):
     """[(name, originals, recovery, intended status, max_rows values)] of one stripe under the two
-    masks.  Absent originals hold junk in every case, and so do unselected recovery rows."""
+    masks.  Absent originals hold junk in every case, and so do unselected recovery rows.  wide: the
+    positional cases of tests/test_gpu_locate_degraded.py's cases, max_rows 0."""
+    if wide:
+        return [c + ([0],) for c in LD.cases(rate, N, M, S, present, mask, wide=True)]
     orig, rec = (x.copy() for x in V.stripe(rate, N, M, S))
     pb, R, K = DM.split(present, mask, M)
     rng = np.random.default_rng(N * 7 + M + S + len(R))
@@ -200,14 +203,15 @@ def compare(what, got, want):
             assert not rows, f"{what}: {name} differs from the model in rows {rows[:8]}"
 
 
-def check_case(torch, rs, rate, N, M, S, pad, present, mask, name, orig, rec, intended, max_rows_list):
+def check_case(torch, rs, rate, N, M, S, pad, present, mask, name, orig, rec, intended, max_rows_list, modes=None):
+    """(modes: the mode values to run, MODES by default.)"""
     pb = np.asarray(present) != 0
     clean_orig, clean_rec = V.stripe(rate, N, M, S)
     base = HDM.found(rate, orig, present, rec, mask)
     assert base[0] == intended, f"{name}: the model says {base[0]}, the case was built for {intended}"
     sel = np.ones(M, bool) if mask is None else np.asarray(mask) != 0
     for form in FORMS:
-        for mode in MODES:
+        for mode in modes or MODES:
             for max_rows in max_rows_list:
                 what = (f"{rate} {N}:{M} x {S} pad {pad} m {int((~pb).sum())} {name} d_restored {form} mode {mode} "
                         f"max_rows {max_rows}")

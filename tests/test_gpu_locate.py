@@ -16,6 +16,7 @@ import locate_model as LM
 import oracle_lib as O
 import span_cases as SC
 import test_gpu_verify as V
+import wide_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -73,11 +74,14 @@ def damage_original(orig, i, form, rng):
         orig[i] ^= rng.integers(1, 256, S, dtype=np.uint8)
 
 
-def cases(rate, N, M, S):
+def cases(rate, N, M, S, wide=False):
     """[(name, originals, recovery, intended status or None)] of one stripe.  The intended status
     is what the case is built to show; None where the shape is too small for the case to mean one
-    thing (two rows in all: "every row differs" may be one original's doing)."""
+    thing (two rows in all: "every row differs" may be one original's doing).  wide: the positional
+    cases of tests/wide_cases.py instead, damage placed by pack number."""
     orig, rec = V.stripe(rate, N, M, S)
+    if wide:
+        return W.locate_cases(orig, rec, CLEAN, ROWS, UNKNOWN)
     rng = np.random.default_rng(N * 7 + M + S)
     out = [("none", orig, rec, CLEAN)]
     for i in sorted({0, N // 2, N - 1}):
@@ -141,8 +145,8 @@ def locate_one(torch, rs, rate, N, M, S, orig, rec, pad=0, mask=None, what="", s
     return int(got[0]), got_flags
 
 
-def run_cases(torch, rs, rate, N, M, S, pad=0, mask=None, only=None):
-    for name, orig, rec, intended in cases(rate, N, M, S):
+def run_cases(torch, rs, rate, N, M, S, pad=0, mask=None, only=None, wide=False):
+    for name, orig, rec, intended in cases(rate, N, M, S, wide):
         if only and not any(name.startswith(o) for o in only):
             continue
         what = f"{rate} {N}:{M} x {S} pad {pad} {name}"
@@ -255,8 +259,9 @@ def check_masks(torch, rs, rate, N, M, S, pad):
         assert got == N // 3 and np.array_equal(flags, mask)
 
 
-def batch_case(rate, N, M, S, B):
-    """B stripes (5..8) with a different outcome and a different i in each."""
+def batch_case(rate, N, M, S, B, wide=False):
+    """B stripes (up to 8) with a different outcome and a different i in each.  wide: the ROWS
+    stripe's row is damaged in the last pack (tests/wide_cases.py), not in the first."""
     rng = np.random.default_rng(B)
     kinds = [("orig", 0, "lastbit"), ("none",), ("rec",), ("orig", N - 1, "shard"), ("two",), ("orig", N // 2, "lastpack"),
              ("orig", N // 3, "highhalf"), ("every",)][:B]
@@ -267,7 +272,10 @@ def batch_case(rate, N, M, S, B):
             damage_original(o, k[1], k[2], rng)
             want = k[1]
         elif k[0] == "rec":
-            r[M // 2, 3 % S] ^= 0x02
+            if wide:
+                W.damage_pack(r, M // 2, W.packs_of(S) - 1, rng)
+            else:
+                r[M // 2, 3 % S] ^= 0x02
             want = ROWS
         elif k[0] == "two":
             o[0, 0] ^= 0x10
@@ -287,10 +295,12 @@ def batch_case(rate, N, M, S, B):
 @pytest.mark.parametrize("rate,N,M,S,B,pad", [("default", 1024, 1024, 72, 6, 0), ("high", 70, 100, 66, 8, 4),
                                               ("high", 1000, 100, 66, 5, 0), ("default", 4096, 4096, 64, 5, 0)],
                          ids=lambda v: str(v))
-def test_batch(torch, rs, rate, N, M, S, B, pad):
+def test_batch(torch, rs, rate, N, M, S, B, pad, wide=False, groups=None):
     """A one-launch shape and stripe-by-stripe shapes, with stripe padding: the constructed
-    results, which are also those of a loop of single calls."""
-    origs, recs, want, want_flags = batch_case(rate, N, M, S, B)
+    results, which are also those of a loop of single calls.  (wide, groups:
+    tests/test_gpu_wide_shards.py's -- batch_case's wide form, and the number of groups the batch
+    must run in.)"""
+    origs, recs, want, want_flags = batch_case(rate, N, M, S, B, wide)
     d_orig, d_rec = V.padded_batch(torch, origs, 2, pad), V.padded_batch(torch, recs, 3, pad)
     loc, loc_buf = guarded(torch, (B,), torch.int32)
     flags, flag_buf = guarded(torch, (B, M), torch.uint8)
@@ -304,6 +314,7 @@ def test_batch(torch, rs, rate, N, M, S, B, pad):
     count = names.count("k_locate_find")
     assert count == names.count("k_locate_confirm") == names.count("k_verify_rows"), names
     assert count == {1024: 1, 1000: B}.get(N, count) and count in (1, B), names
+    assert groups is None or count == groups, names
     for b in range(B):
         single, single_flags = locate_one(torch, rs, rate, N, M, S, origs[b], recs[b], pad, what=f"stripe {b}")
         assert single == got[b] and np.array_equal(single_flags, got_flags.reshape(B, M)[b])

@@ -16,6 +16,7 @@ import locate_degraded_model as DM
 import locate_model as LM
 import oracle_lib as O
 import test_gpu_verify as V
+import wide_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -89,9 +90,12 @@ def third_mask(M):
     return mask
 
 
-def cases(rate, N, M, S, present, mask):
+def cases(rate, N, M, S, present, mask, wide=False):
     """[(name, originals, recovery, intended status)] of one stripe under the two masks.  Absent
-    originals hold junk in every case, and so do unselected recovery rows."""
+    originals hold junk in every case, and so do unselected recovery rows.  wide: the positional
+    cases of a wide shard instead (tests/wide_cases.py) -- clean; a present original damaged in the
+    last pack, and as a whole shard; a reference row damaged in pack 256 (the last pack where the
+    shard has no second tile) and another in the last pack."""
     orig, rec = (x.copy() for x in V.stripe(rate, N, M, S))
     pb, R, K = DM.split(present, mask, M)
     rng = np.random.default_rng(N * 7 + M + S + len(R))
@@ -101,6 +105,22 @@ def cases(rate, N, M, S, present, mask):
         rec[unsel] ^= rng.integers(1, 256, (int(unsel.sum()), S), dtype=np.uint8)
     have = np.flatnonzero(pb)
     out = [("clean", orig, rec, CLEAN)]
+    if wide:
+        packs = W.packs_of(S)
+        bad = orig.copy()
+        W.damage_pack(bad, have[-1], packs - 1, rng)
+        out.append((f"original {have[-1]} pack {packs - 1}", bad, rec, int(have[-1])))
+        bad = orig.copy()
+        bad[have[len(have) // 2]] ^= rng.integers(1, 256, S, dtype=np.uint8)
+        out.append((f"original {have[len(have) // 2]} shard", bad, rec, int(have[len(have) // 2])))
+        p = W.TILE if W.TILE < packs else packs - 1
+        bad = rec.copy()
+        W.damage_pack(bad, R[0], p, rng)
+        out.append((f"reference row {R[0]} pack {p}", orig, bad, N + int(R[0])))
+        bad = rec.copy()
+        W.damage_pack(bad, R[-1], packs - 1, rng)
+        out.append((f"reference row {R[-1]} pack {packs - 1}", orig, bad, N + int(R[-1])))
+        return out
     if len(have):
         bad = orig.copy()
         bad[have[0], 0] ^= 0x01  # one bit in byte 0

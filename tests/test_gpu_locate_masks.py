@@ -38,10 +38,12 @@ def guarded_located(torch, n):
     return buf[4:4 + n], buf
 
 
-def run(torch, rs, rate, N, M, S, pad):
+def run(torch, rs, rate, N, M, S, pad, batch=None):
     """One status-mode call on fresh, stripe-padded device copies, checked against the constructed
-    outcome and for stray writes; (located, flags, codes, records, device matrices)."""
-    _, _, store, held, masks, intent, want = C.locate_batch(rate, N, M, S)
+    outcome and for stray writes; (located, flags, codes, records, device matrices).  batch: (stored
+    originals, stored recovery, masks, intended located, expected flags) in place of
+    C.locate_batch's."""
+    store, held, masks, intent, want = batch or C.locate_batch(rate, N, M, S)[2:]
     B = len(masks)
     d_orig, d_rec = padded_batch(torch, np.array(store), 2, pad), padded_batch(torch, np.array(held), 3, pad)
     flags, buf = guarded_flags(torch, (B, M))

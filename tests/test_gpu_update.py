@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import wide_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -71,10 +72,14 @@ def indices(N, count, rng):
     return idx
 
 
-def change(rate, N, M, S, idx, seed=0):
-    """(old rows, new rows, wanted recovery) for overwriting originals idx of the stripe."""
+def change(rate, N, M, S, idx, seed=0, positional=False):
+    """(old rows, new rows, wanted recovery) for overwriting originals idx of the stripe.
+    positional: the first new row differs from the old one in the last pack only and the second in
+    pack 0 only (tests/wide_cases.py update_new_rows)."""
     orig, _ = stripe(rate, N, M, S, seed)
     new = O.generate_original(len(idx), S, seed + 17)
+    if positional:
+        new = W.update_new_rows(orig[idx], new)
     mod = orig.copy()
     mod[idx] = new
     return np.ascontiguousarray(orig[idx]), new, O.encode(rate, mod, M)
@@ -95,13 +100,14 @@ def check(got, want, what):
         raise AssertionError(f"{what}: " + first_diff(got.reshape(-1, got.shape[-1]), want.reshape(-1, want.shape[-1])))
 
 
-def run(torch, rs, rate, N, M, S, idx, route, form="delta", mask=None, seed=0):
+def run(torch, rs, rate, N, M, S, idx, route, form="delta", mask=None, seed=0, positional=False, pad=0):
     """One update on fresh device copies; returns the recovery matrix after it.  Also checks that
-    the inputs and the unselected rows are as before."""
-    old, new, want = change(rate, N, M, S, idx, seed)
+    the inputs and the unselected rows are as before, and with `pad` bytes of 0xC3 after every
+    recovery row, that those are."""
+    old, new, want = change(rate, N, M, S, idx, seed, positional)
     _, rec = stripe(rate, N, M, S, seed)
     rs.update_set_direct_max(route)
-    d_rec = dev(torch, rec)
+    d_rec, b_rec = view(torch, rec, 0, pad)
     if form == "delta":
         h_old, h_new = None, old ^ new
     else:
@@ -115,6 +121,7 @@ def run(torch, rs, rate, N, M, S, idx, route, form="delta", mask=None, seed=0):
     sel = np.ones(M, bool) if mask is None else np.asarray(mask) != 0
     check(got[sel], want[sel], what)
     check(got[~sel], rec[~sel], what + ": an unselected row was written")
+    assert (padding_of(b_rec, rec, 0, pad) == 0xC3).all(), what + ": recovery padding written"
     check(d_new.cpu().numpy(), h_new, what + ": d_new was written")
     if d_old is not None:
         check(d_old.cpu().numpy(), h_old, what + ": d_old was written")

@@ -14,6 +14,7 @@ import pytest
 
 import oracle_lib as O
 import span_cases as SC
+import wide_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -64,8 +65,14 @@ def stripe(rate, N, M, S, seed=0):
 
 
 def corrupt(kind, rate, N, M, S, seed=0):
-    """(originals, recovery, expected flags) of the stripe after one corruption."""
+    """(originals, recovery, expected flags) of the stripe after one corruption.  A tuple is one of
+    tests/wide_cases.py's positional kinds: damage placed by pack number."""
     orig, rec = stripe(rate, N, M, S, seed)
+    if isinstance(kind, tuple):
+        key = (kind, rate, N, M, S, seed)
+        if key not in _WANT_ORIGINAL:
+            _WANT_ORIGINAL[key] = W.verify_corrupt(kind, orig, rec, lambda o: O.encode(rate, o, M))
+        return tuple(a.copy() for a in _WANT_ORIGINAL[key])
     orig, rec = orig.copy(), rec.copy()
     want = np.zeros(M, np.uint8)
     if kind == "first":  # one bit in row 0, byte 0
@@ -272,9 +279,9 @@ def check_masks(torch, rs, rate, N, M, S, fused):
     assert (h[:GUARD] == 0xFF).all() and (h[-GUARD:] == 0xFF).all() and not h[GUARD:-GUARD].any()
 
 
-def batch_case(rate, N, M, S):
-    """3 stripes, a different corruption in each, one of them clean."""
-    kinds = ["middle", "none", "last"]
+def batch_case(rate, N, M, S, B=3):
+    """B stripes (3 by default), a different corruption in each of three neighbours, one of them clean."""
+    kinds = (["middle", "none", "last"] * ((B + 2) // 3))[:B]
     parts = [corrupt(k, rate, N, M, S, seed=b) for b, k in enumerate(kinds)]
     return tuple(np.stack([p[i] for p in parts]) for i in range(3))
 
@@ -292,21 +299,32 @@ def padded_batch(torch, a, extra, pad=0):
 @pytest.mark.parametrize("rate,N,M,S", [("high", 70, 100, 64), ("default", 1024, 1024, 72), ("high", 1000, 100, 66)],
                          ids=lambda v: str(v))
 def test_batch(torch, rs, rate, N, M, S, fused):
-    origs, recs, wants = batch_case(rate, N, M, S)
-    d_orig, d_rec = padded_batch(torch, origs, 2), padded_batch(torch, recs, 3)
-    flags, buf = guarded_flags(torch, (3, M))
+    check_batch(torch, rs, rate, N, M, S, fused)
+
+
+def check_batch(torch, rs, rate, N, M, S, fused, B=3, pad=0, singles=False):
+    """test_batch's body; the launch names of the batch call.  (B, pad, singles:
+    tests/test_gpu_wide_shards.py's -- more stripes, row padding, and every stripe's flags against a
+    verify_device of that stripe alone.)"""
+    origs, recs, wants = batch_case(rate, N, M, S, B)
+    d_orig, d_rec = padded_batch(torch, origs, 2, pad), padded_batch(torch, recs, 3, pad)
+    flags, buf = guarded_flags(torch, (B, M))
     rs.verify_set_fused(fused)
-    rs.verify_device_batch(N, M, S, d_orig, d_rec, d_mismatch=flags, rate_=RATE[rate])
-    torch.cuda.synchronize()
+    names = [r[0] for r in profiled(torch, rs, lambda: rs.verify_device_batch(N, M, S, d_orig, d_rec, d_mismatch=flags,
+                                                                              rate_=RATE[rate]))]
     got = check_untouched(buf, flags, d_orig, origs, d_rec, recs, "batch")
-    for b in range(3):
+    for b in range(B):
         assert np.array_equal(got[b], wants[b]), (b, np.flatnonzero(got[b])[:8], np.flatnonzero(wants[b])[:8])
+        if singles:
+            alone = rs.verify_device(N, M, S, d_orig[b], d_rec[b], rate_=RATE[rate]).cpu().numpy()
+            assert np.array_equal(alone, got[b]), f"stripe {b} alone: {np.flatnonzero(alone)[:8]}"
     # one mask for every stripe, and a tensor the call allocates itself
     mask = np.ones(M, np.uint8)
     mask[M // 2] = 0
     got = rs.verify_device_batch(N, M, S, d_orig, d_rec, recovery_rows=mask, rate_=RATE[rate])
-    assert got.shape == (3, M) and str(got.dtype) == "torch.uint8" and got.is_cuda
+    assert got.shape == (B, M) and str(got.dtype) == "torch.uint8" and got.is_cuda
     assert np.array_equal(got.cpu().numpy(), wants * mask)
+    return names
 
 
 def test_launches(torch, rs):

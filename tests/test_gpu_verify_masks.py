@@ -34,9 +34,10 @@ def rs(torch):
     reed_solomon_simd.mono_enable(True)
 
 
-def run(torch, rs, rate, N, M, S, pad, fused):
-    """One call on fresh, stripe-padded device copies; (flags, launch records)."""
-    _, _, store, held, masks, want = C.verify_batch(rate, N, M, S)
+def run(torch, rs, rate, N, M, S, pad, fused, batch=None):
+    """One call on fresh, stripe-padded device copies; (flags, launch records).  batch: (stored
+    originals, stored recovery, masks, expected flags) in place of C.verify_batch's."""
+    store, held, masks, want = batch or C.verify_batch(rate, N, M, S)[2:]
     B = len(masks)
     d_orig, d_rec = padded_batch(torch, np.array(store), 2, pad), padded_batch(torch, np.array(held), 3, pad)
     flags, buf = guarded_flags(torch, (B, M))
