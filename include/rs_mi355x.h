@@ -1610,12 +1610,23 @@ rs_status rs_check_device(rs_context *ctx);
  * entry, which takes the row maps' geometry as decided by the host instead of
  * testing it per lane (on by default; RS_MI355X_DENSE=0 at context creation:
  * never): adding 8192 turns it on, adding 16384 off (the general entry).
+ * Where the dense entry runs an encode of N = M = 2^10 shards in 2-element
+ * column packs (at most half the device's CUs in 8-byte packs), one stripe, its
+ * split form can run instead: a pair of rows' two byte planes on neighbouring
+ * lanes, half multiplies (RS_ENC_SPLIT_DEFAULT; RS_MI355X_ENC_SPLIT=0/1 at
+ * context creation): adding 32768 turns it on, adding 65536 off.  With the dense
+ * entry off the split form is off too.
  * Neither bit of a pair: the context's defaults (its environment included).
  * A/B and tests; results are identical in every mode. */
 rs_status rs_mono_enable(rs_context *ctx, int enable);
 /* Launches of the dense entry by this process so far (tests, A/B: the profile
- * records name the general and the dense entry alike, k_mono<...>). */
+ * records name the general and the dense entry alike, k_mono<...>).  A launch
+ * of the split form counts here too. */
 uint64_t rs_mono_dense_launches(void);
+/* The split form of the dense entry: the default of a new context (measured,
+ * DESIGN.md 9), and its launches by this process so far. */
+#define RS_ENC_SPLIT_DEFAULT 1
+uint64_t rs_mono_split_launches(void);
 
 /* ---- GF(2^16) tables (src/engine/tables.rs), host copies ---- */
 const uint16_t *rs_table_exp(void);       /* 65536 */

@@ -24,6 +24,7 @@
 #include "../../include/rs_mi355x.h"
 #include "gf_tables.hpp"
 #include "rs_device.hpp"
+#include "rs_stage_map.hpp"
 
 namespace {
 
@@ -394,6 +395,12 @@ struct rs_context {
     // rs_mono_dense.hpp mono_dense_ok holds: N = M = 2^L, shards of whole blocks, aligned
     // (RS_MI355X_DENSE=0/1; rs_mono_enable + 8192: on, + 16384: off)
     bool dense = true, dense_default = true;
+    // split form of that entry (rs_mono.hip k_mono_split: a pair row's two byte planes on
+    // neighbouring lanes) for 2^10 rows in 2-element packs, one stripe, taken only where
+    // the dense entry would be (RS_MI355X_ENC_SPLIT=0/1; rs_mono_enable + 32768: on,
+    // + 65536: off).  The default is measured: DESIGN.md 9
+    bool enc_split = RS_ENC_SPLIT_DEFAULT != 0, enc_split_default = RS_ENC_SPLIT_DEFAULT != 0;
+    uint32_t *d_simg = nullptr;   // its images, skew offsets 0 and 2^10 (split_images)
     // multi-chunk encodes of 2^2..2^7-row transforms on k_chunks (use_chunks below;
     // RS_MI355X_CHUNKS=0/1; rs_mono_enable + 512: on, + 1024: off)
     bool chunks = true, chunks_default = true;
@@ -736,6 +743,30 @@ const uint32_t *mono_images(rs_context *ctx, uint32_t L, uint32_t elems = 4) {
     return d;
 }
 
+// The split encode's images (rs_mono.hip k_mono_split; rs_stage_map.hpp SplitImage: the
+// staged regions' contents in the order the LDS-DMA fill wants) for the two skew offsets
+// a single-chunk encode of 2^10 rows uses, 0 and 2^10; built at context creation.
+constexpr uint32_t kSplitImages = 2;
+const uint32_t *split_images(rs_context *ctx) {
+    std::lock_guard<std::mutex> lock(ctx->img_mu);
+    if (ctx->d_simg) return ctx->d_simg;
+    using SI = rs::SplitImage<10>;
+    const rs::GfTables &T = rs::tables();
+    std::vector<uint32_t> h(size_t(SI::kWords) * kSplitImages);
+    for (uint32_t t = 0; t < kSplitImages; ++t)
+        rs::split_image_fill<10>(&h[size_t(t) * SI::kWords], t, T.perm_by_skew.data(), T.perm2_by_skew.data());
+    uint32_t *d = nullptr;
+    check(hipMalloc(&d, h.size() * 4));
+    check(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    ctx->d_simg = d;
+    return d;
+}
+// (null: the split form is switched off, or the dense entry is)
+const uint32_t *split_images_if(rs_context *ctx, const rs::MonoArgs &M) {
+    return ctx->enc_split && ctx->dense && M.ifft_img < kSplitImages && M.fft_img < kSplitImages ? split_images(ctx)
+                                                                                                 : nullptr;
+}
+
 // Basis images (the 2-element staged kernels' twiddles: k_mono, rs_mono.hip
 // basis_expand, and k_chunks): the layout of mono_images, 8 words per table -- the
 // products P(e_i) = x * e_i of the table's multiplier with the 16 Cantor basis
@@ -851,10 +882,11 @@ rs::MonoArgs mono_args(rs_context *ctx, uint32_t L, const Geom &g, bool staged, 
     return M;
 }
 
-void launch_mono(int mode, uint32_t L, const rs::MonoArgs &M, hipStream_t s, uint64_t bytes) {
+void launch_mono(int mode, uint32_t L, const rs::MonoArgs &M, hipStream_t s, uint64_t bytes,
+                 const uint32_t *split_img = nullptr) {
     hipEvent_t ev = nullptr;
     if (t_prof_ctx) prof_begin(s, &ev);
-    check(rs::launch_mono(mode, int(L), M, s));
+    check(rs::launch_mono(mode, int(L), M, s, split_img));
     if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), bytes);
 }
 
@@ -1065,7 +1097,8 @@ void encode_high(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint
         Mo.fft_img = 0;
         const uint64_t bytes = (N + out_hi - out_lo) * uint64_t(g.packs) * 8 * g.stripes;
         if (!try_quad(ctx, L, C, Mo, s, bytes) && !try_lane(ctx, L, C, Mo, s, bytes))
-            launch_mono(rs::kMonoEncodeHigh | (ctx->dense ? 0 : rs::kMonoNoDense), L, Mo, s, bytes);
+            launch_mono(rs::kMonoEncodeHigh | (ctx->dense ? 0 : rs::kMonoNoDense), L, Mo, s, bytes,
+                        split_images_if(ctx, Mo));
         return;
     }
     if (use_chunks(ctx, L, g, C, true)) {
@@ -1162,7 +1195,8 @@ void encode_low(rs_context *ctx, Workspace &ws, const Geom &g, uint64_t N, uint6
         Mo.fft_img_step = 1;
         const uint64_t bytes = (N + out_hi - out_lo) * uint64_t(g.packs) * 8 * g.stripes;
         if (!try_quad(ctx, L, C, Mo, s, bytes) && !try_lane(ctx, L, C, Mo, s, bytes))
-            launch_mono(rs::kMonoEncodeLow | (ctx->dense ? 0 : rs::kMonoNoDense), L, Mo, s, bytes);
+            launch_mono(rs::kMonoEncodeLow | (ctx->dense ? 0 : rs::kMonoNoDense), L, Mo, s, bytes,
+                        split_images_if(ctx, Mo));
         return;
     }
     if (use_chunks(ctx, L, g, C, false)) {
@@ -2857,6 +2891,8 @@ rs_status rs_context_create(int device, rs_context **out) {
         ctx->quad_default = ctx->quad;
         if (const char *de = getenv("RS_MI355X_DENSE")) ctx->dense = de[0] == '1';
         ctx->dense_default = ctx->dense;
+        if (const char *sp = getenv("RS_MI355X_ENC_SPLIT")) ctx->enc_split = sp[0] == '1';
+        ctx->enc_split_default = ctx->enc_split;
         if (const char *ck = getenv("RS_MI355X_CHUNKS")) {  // 0 off, 1 default routing, 2 every supported shape
             ctx->chunks = ck[0] != '0';
             ctx->chunks_forced = ck[0] == '2';
@@ -2898,6 +2934,7 @@ rs_status rs_context_create(int device, rs_context **out) {
         for (uint32_t L = kChunksMinL; L <= 11; ++L) mono_images(ctx, L, 2);
         for (uint32_t L = kChunksMinL; L <= (RS_MONO_BASIS ? 11u : 10u); ++L) basis_images(ctx, L);  // (k_lane: 8..10)
         for (uint32_t L = kChunksMinL; L <= 7; ++L) basis_images(ctx, L, 4);
+        split_images(ctx);
         return RS_OK;
     });
     if (st != RS_OK) {
@@ -2920,6 +2957,7 @@ void rs_context_destroy(rs_context *ctx) {
     if (ctx->d_twb) (void)hipFree(ctx->d_twb);
     if (ctx->d_lutb) (void)hipFree(ctx->d_lutb);
     if (ctx->d_top) (void)hipFree(ctx->d_top);
+    if (ctx->d_simg) (void)hipFree(ctx->d_simg);
     for (uint32_t *p : ctx->d_img2)
         if (p) (void)hipFree(p);
     for (uint32_t *p : ctx->d_imgb)
@@ -4688,6 +4726,8 @@ rs_status rs_mono_enable(rs_context *ctx, int enable) {
     ctx->quad = (enable & 2048) ? true : (enable & 4096) ? false : ctx->quad_default;
     // + 8192: dense encode entry on, + 16384: off
     ctx->dense = (enable & 8192) ? true : (enable & 16384) ? false : ctx->dense_default;
+    // + 32768: split form of the dense entry on, + 65536: off
+    ctx->enc_split = (enable & 32768) ? true : (enable & 65536) ? false : ctx->enc_split_default;
     // + 512: multi-chunk kernel on, + 1024: off
     ctx->chunks = (enable & 512) ? true : (enable & 1024) ? false : ctx->chunks_default;
     // (neither bit: the context's defaults, RS_MI355X_CHUNKS=2's forced routing included)
@@ -4696,6 +4736,7 @@ rs_status rs_mono_enable(rs_context *ctx, int enable) {
 }
 
 uint64_t rs_mono_dense_launches(void) { return rs::mono_dense_launches(); }
+uint64_t rs_mono_split_launches(void) { return rs::mono_split_launches(); }
 
 rs_status rs_check_device(rs_context *ctx) {
     if (!ctx) return RS_ERR_INVALID_ARGUMENT;

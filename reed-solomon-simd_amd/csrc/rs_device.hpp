@@ -329,7 +329,13 @@ struct MonoArgs : MonoCore {
     uint32_t erased[kMonoFusedRows / 32] = {}, received[kMonoFusedRows / 32] = {};
 };
 // hipErrorNotSupported: no column kernel for this L (7 <= L <= 12 are built).
-hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t stream);
+// split_img (encodes): the context's split images (rs_stage_map.hpp SplitImage, image t
+// at split_img + t * SplitImage<10>::kWords); where the dense entry would run a launch
+// of 2^10 rows in 2-element packs, one stripe, its split form runs instead (rs_mono.hip
+// k_mono_split).  nullptr: never.
+hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t stream, const uint32_t *split_img = nullptr);
+// launches of the split form so far (each also counts in mono_dense_launches)
+uint64_t mono_split_launches();
 // Repair (rs_repair_device*): the decode kernels with a second destination map,
 // dst2 over the recovery rows' work-row range (dst: the originals').  A row is
 // stored to the map that holds it when it is erased; rows of neither map (the

@@ -196,4 +196,43 @@ __device__ __forceinline__ void fft_bfly(uint32_t &al, uint32_t &ah, uint32_t &b
     bh ^= ah;
 }
 
+// One byte plane of a 4-element multiply (the split encode, rs_mono.hip k_mono_split).
+// gf_muladd4 is four independent quarters -- (input plane, output plane) -> table words
+// low/low 0-4, low/high 5-9, high/low 10-14, high/high 15-19 -- so the two planes of a
+// word pair can live in two lanes: a lane forms the two quarters that start from its
+// own plane x, `own` (the product's part in the same plane) and `other` (the part in
+// the neighbour's plane), from the ten words h of its half of the table, own's five
+// first: the low plane's half is words 0-9, the high plane's words 15-19, 10-14
+// (rs_stage_map.hpp SplitImage stages them so).  m7 / m3: 0x07070707 / 0x03030303,
+// held in SGPRs by the caller; 32-bit shifts suffice for one plane (no field of the
+// masks crosses a byte).  5 VOP2, 6 v_perm_b32, 2 v_bitop3.
+__device__ __forceinline__ void gf_half_mul(uint32_t x, const uint32_t *__restrict__ h, uint32_t m7, uint32_t m3,
+                                            uint32_t &own, uint32_t &other) {
+    const uint32_t s0 = x & m7, s1 = (x >> 3) & m7, s2 = (x >> 6) & m3;
+    own = xor3(__builtin_amdgcn_perm(h[1], h[0], s0), __builtin_amdgcn_perm(h[3], h[2], s1),
+               __builtin_amdgcn_perm(h[4], h[4], s2));
+    other = xor3(__builtin_amdgcn_perm(h[6], h[5], s0), __builtin_amdgcn_perm(h[8], h[7], s1),
+                 __builtin_amdgcn_perm(h[9], h[9], s2));
+}
+// acc ^= this plane of (x, neighbour's x) * m: own, and the neighbour lane's `other`
+// (lane ^ 1: the word pair's planes sit on lane bit 0) through a DPP XOR
+__device__ __forceinline__ void gf_half_muladd(uint32_t &acc, uint32_t x, const uint32_t *__restrict__ h, uint32_t m7,
+                                               uint32_t m3) {
+    uint32_t own, other;
+    gf_half_mul(x, h, m7, m3, own, other);
+    acc ^= xor_lane<0>(other);
+    acc ^= own;
+}
+// ifft_bfly / fft_bfly on one plane per lane
+__device__ __forceinline__ void ifft_bfly_half(uint32_t &a, uint32_t &b, const uint32_t *__restrict__ h, uint32_t m7,
+                                               uint32_t m3) {
+    b ^= a;
+    gf_half_muladd(a, b, h, m7, m3);
+}
+__device__ __forceinline__ void fft_bfly_half(uint32_t &a, uint32_t &b, const uint32_t *__restrict__ h, uint32_t m7,
+                                              uint32_t m3) {
+    gf_half_muladd(a, b, h, m7, m3);
+    b ^= a;
+}
+
 }  // namespace rs

@@ -29,6 +29,7 @@
 #include "rs_device.hpp"
 #include "rs_gf.hpp"
 #include "rs_mono_dense.hpp"
+#include "rs_mono_plan.hpp"
 #include "rs_stage_map.hpp"
 
 namespace rs {
@@ -49,177 +50,6 @@ __device__ uint64_t g_mono_stamps[4096][24];
 #else
 #define RS_MSTAMP(i)
 #endif
-
-// ---------------------------------------------------------------------------
-// compile-time plan
-
-struct Map {
-    int reg[3];   // row bit held by register-index bit s
-    int lane[6];  // row bit held by lane bit j
-    int wave[4];  // row bit held by wave bit k
-};
-enum : int { kOpLayer = 1, kOpXpose = 2, kOpRemap = 3 };
-struct Op {
-    int kind, bit, rs, ls;  // layer on `bit` (register bit rs) / swap register bit rs with lane bit ls
-};
-constexpr int kMaxOps = 64;
-struct Seq {
-    int count = 0;
-    Op ops[kMaxOps] = {};
-    Map maps[kMaxOps + 1] = {};  // maps[i]: placement before op i; maps[count]: final
-};
-
-constexpr int find_reg(const Map &m, int LR, int x) {
-    for (int s = 0; s < LR; ++s)
-        if (m.reg[s] == x) return s;
-    return -1;
-}
-constexpr int find_lane(const Map &m, int x) {
-    for (int j = 0; j < 6; ++j)
-        if (m.lane[j] == x) return j;
-    return -1;
-}
-constexpr int next_use(const int *bits, int nb, int from, int x) {
-    for (int t = from; t < nb; ++t)
-        if (bits[t] == x) return t;
-    return 1 << 20;
-}
-constexpr void push(Seq &s, Op op, const Map &after) {
-    s.ops[s.count] = op;
-    ++s.count;
-    s.maps[s.count] = after;
-}
-
-// Butterfly layers on `bits` in order; a bit not in a register is swapped in
-// from its lane bit, evicting the register bit used furthest in the future.
-constexpr void layers(Seq &s, Map &m, int LR, const int *bits, int nb) {
-    for (int t = 0; t < nb; ++t) {
-        const int x = bits[t];
-        int rs = find_reg(m, LR, x);
-        if (rs < 0) {
-            const int j = find_lane(m, x);
-            int far = -1;
-            for (int q = 0; q < LR; ++q) {
-                const int u = next_use(bits, nb, t + 1, m.reg[q]);
-                if (u > far) far = u, rs = q;
-            }
-            const int tmp = m.reg[rs];
-            m.reg[rs] = m.lane[j];
-            m.lane[j] = tmp;
-            push(s, Op{kOpXpose, x, rs, j}, m);
-        }
-        push(s, Op{kOpLayer, x, rs, 0}, m);
-    }
-}
-
-// Placement of a segment: in-wave bits [lo, lo + IW), wave bits the rest.
-// Registers take the first bits of `order`; lane bits the next ones, cheapest
-// transposes (permlane swaps: lane bits 5, 4; DPP: 0, 1, 3; two DPP moves: 2) first.
-constexpr Map seg_map(int L, int LR, int lo, const int *order, int no) {
-    const int IW = LR + 6;
-    int pri[16] = {}, np = 0;
-    for (int t = 0; t < no; ++t) {
-        const int x = order[t];
-        bool seen = x < lo || x >= lo + IW;
-        for (int q = 0; q < np; ++q) seen = seen || pri[q] == x;
-        if (!seen) pri[np++] = x;
-    }
-    for (int x = lo; x < lo + IW; ++x) {
-        bool seen = false;
-        for (int q = 0; q < np; ++q) seen = seen || pri[q] == x;
-        if (!seen) pri[np++] = x;
-    }
-    const int pref[6] = {5, 4, 0, 1, 3, 2};
-    Map m{};
-    for (int s = 0; s < 3; ++s) m.reg[s] = s < LR ? pri[s] : -1;
-    for (int j = 0; j < 6; ++j) m.lane[pref[j]] = pri[LR + j];
-    int k = 0;
-    for (int x = 0; x < L; ++x)
-        if (x < lo || x >= lo + IW) m.wave[k++] = x;
-    for (; k < 4; ++k) m.wave[k] = -1;
-    return m;
-}
-
-// SPLIT (decodes whose restored rows lie in one half of the 2^L work rows):
-// the top row bit L-1 stays a wave bit throughout, so each half is a 2^(L-1)
-// row transform of its own waves; the IFFT stops below layer L-1, the top
-// layers of both transforms and the formal derivative's cross-half term run
-// in one exchange (split_top), and only the half holding restored rows runs
-// the rest of the FFT.
-// SP bit 1 (FLOW, decodes): the FFT leaves the top placement after layer IW
-// instead of WB, so its layers IW-1..0 run with the low bits in-wave -- each
-// wave then holds 2^IW consecutive rows, the waves without restored rows stop
-// there, and those layers reuse the IFFT's phase-1 tables
-template <int L, int LR, int SP = 0>
-struct Plan {
-    static constexpr bool SPLIT = (SP & 1) != 0, FLOW = (SP & 2) != 0;
-    static constexpr int IW = LR + 6, WB = L - IW - (SPLIT ? 1 : 0), R = 1 << LR;
-    static_assert(WB >= 0 && L - IW <= 4, "column kernel: 6 lane bits + LR register bits + up to 4 wave bits");
-    static_assert(!SPLIT || WB >= 1, "split plan: at least one wave bit below the top bit");
-    static constexpr int TOP = SPLIT ? L - 1 : L;  // layers [0, TOP) run in the sequences
-    // lowest FFT layer of the top placement (the FFT's low segment: layers FLO-1..0)
-    static constexpr int FLO = FLOW && WB > 0 ? IW : WB;
-
-    static constexpr Seq make_ifft() {
-        Seq s{};
-        int bits[16] = {}, order[32] = {}, no = 0;
-        if (WB == 0 && !SPLIT) {
-            for (int x = 0; x < L; ++x) order[no++] = x;
-            for (int x = L - 1; x >= 0; --x) order[no++] = x;
-            Map m = seg_map(L, LR, 0, order, no);
-            s.maps[0] = m;
-            for (int x = 0; x < L; ++x) bits[x] = x;
-            layers(s, m, LR, bits, L);
-            return s;
-        }
-        // segment A: IFFT layers 0..IW-1 with the low bits in-wave
-        for (int x = 0; x < IW; ++x) order[no++] = x, bits[x] = x;
-        Map m = seg_map(L, LR, 0, order, no);
-        s.maps[0] = m;
-        layers(s, m, LR, bits, IW);
-        // segment B: the top IW bits (below bit L-1 when SPLIT) in-wave: IFFT
-        // layers IW..TOP-1 (then FFT TOP-1..WB)
-        no = 0;
-        for (int x = IW; x < TOP; ++x) order[no++] = x;
-        for (int x = TOP - 1; x >= WB; --x) order[no++] = x;
-        m = seg_map(L, LR, WB, order, no);
-        push(s, Op{kOpRemap, -1, 0, 0}, m);
-        for (int x = IW; x < TOP; ++x) bits[x - IW] = x;
-        layers(s, m, LR, bits, TOP - IW);
-        return s;
-    }
-    static constexpr Seq ifft = make_ifft();
-
-    static constexpr Seq make_fft() {
-        Seq s{};
-        int bits[16] = {}, order[16] = {}, no = 0;
-        Map m = ifft.maps[ifft.count];
-        s.maps[0] = m;
-        const int stop = FLO;  // FFT layers TOP-1..stop in the IFFT's final placement
-        for (int x = TOP - 1; x >= stop; --x) bits[TOP - 1 - x] = x;
-        layers(s, m, LR, bits, TOP - stop);
-        if (WB == 0) return s;
-        // segment C: the low IW bits in-wave again, FFT layers FLO-1..0
-        for (int x = FLO - 1; x >= 0; --x) order[no++] = x;
-        m = seg_map(L, LR, 0, order, no);
-        push(s, Op{kOpRemap, -1, 0, 0}, m);
-        for (int x = FLO - 1; x >= 0; --x) bits[FLO - 1 - x] = x;
-        layers(s, m, LR, bits, FLO);
-        return s;
-    }
-    static constexpr Seq fft = make_fft();
-};
-
-template <int L, int LR, bool FFT, int SPLIT = 0>
-struct SeqOf {
-    static constexpr const Seq &v = FFT ? Plan<L, LR, SPLIT>::fft : Plan<L, LR, SPLIT>::ifft;
-};
-
-constexpr int layer_ordinal(const Seq &s, int i) {
-    int k = 0;
-    for (int q = 0; q < i; ++q) k += s.ops[q].kind == kOpLayer;
-    return k;
-}
 
 // ---------------------------------------------------------------------------
 // device helpers
@@ -279,10 +109,13 @@ __device__ __forceinline__ void xpose(uint32_t &a, uint32_t &b, uint32_t lane) {
 // word [lo0 lo1 hi0 hi1], 16-word tables, gf_muladd2): the 2-element form gives
 // a shard matrix twice the workgroups (packs = shard_bytes / 4), for matrices
 // whose 4-element packs leave CUs idle.
+// E = 1 (the split encode, k_mono_split): a register is one byte plane of a pair row's
+// 4-element word, the other plane is the neighbour lane's (lane ^ 1); a lane reads its
+// plane's half of a 20-word table, 10 words (rs_gf.hpp gf_half_mul).
 template <int E>
 struct Fmt {
-    static_assert(E == 4 || E == 2, "pack format");
-    static constexpr int kTW = E == 4 ? 20 : 16;  // table words
+    static_assert(E == 4 || E == 2 || E == 1, "pack format");
+    static constexpr int kTW = E == 4 ? 20 : E == 2 ? 16 : 10;  // table words (a lane reads)
     static constexpr uint32_t kPC = kTW / 4;      // 16-byte pieces per table
     static constexpr bool kHi = E == 4;           // rows have a separate high-byte word
 };
@@ -292,6 +125,13 @@ struct Col {
     static constexpr int R = 1 << LR;
     static constexpr uint32_t n = 1u << L;
     uint32_t lo[R], hi[E == 4 ? R : 1];
+};
+// one plane per lane: + the field masks of gf_half_mul, which the kernel pins in SGPRs
+template <int L, int LR>
+struct Col<L, LR, 1> {
+    static constexpr int R = 1 << LR;
+    static constexpr uint32_t n = 1u << L;
+    uint32_t lo[R], m7, m3;
 };
 
 // Index of register pair (i, i | 2^s) among the pairs of register bit s.
@@ -530,7 +370,10 @@ __device__ __forceinline__ void apply_layer(const uint32_t (&t)[(1 << LR) / 2][F
         constexpr int i = decltype(ic)::value;
         constexpr int i2 = i | (1 << op.rs);
         if constexpr (!((i >> op.rs) & 1)) {
-            if constexpr (E == 2) {
+            if constexpr (E == 1) {
+                if constexpr (IFFT) ifft_bfly_half(c.lo[i], c.lo[i2], t[pair_of(i, op.rs)], c.m7, c.m3);
+                else fft_bfly_half(c.lo[i], c.lo[i2], t[pair_of(i, op.rs)], c.m7, c.m3);
+            } else if constexpr (E == 2) {
                 if constexpr (IFFT) ifft_bfly2(c.lo[i], c.lo[i2], t[pair_of(i, op.rs)]);
                 else fft_bfly2(c.lo[i], c.lo[i2], t[pair_of(i, op.rs)]);
             } else {
@@ -2922,6 +2765,177 @@ k_mono_dense(const uint8_t *src, uint64_t src_stride, uint8_t *dst, uint64_t dst
     const MonoLeadDense lead{src, src_stride, dst, dst_stride, packs, packs_per_xcd, img, img_words, imgs};
     mono_body<L, LR, MODE, true, BATCH, false, E, false, false, false, true, true>(R, nullptr, &lead);
 }
+// ---------------------------------------------------------------------------
+// Split encode (k_mono_split), a form of the dense entry for 2^10 rows in 2-element
+// column packs, one stripe: the pair-row arithmetic of the quad encode (rows 2q and
+// 2q + 1 as one 4-element word pair, gf_muladd4's 26 VALU for what two gf_muladd2 spend
+// 48 on) at the dense kernel's 512 threads.  The two byte planes of a pair row sit on
+// neighbouring lanes -- even lane: low bytes, odd lane: high bytes, lane bit 0 is the
+// plane from the loads to the stores (Plan's PAIR kind) -- and a register is one plane:
+// [row 2q elem 0, row 2q elem 1, row 2q + 1 elem 0, row 2q + 1 elem 1].  A butterfly of
+// layers 1..9 multiplies with a half table (rs_gf.hpp gf_half_mul: the two quarters that
+// start from the lane's plane) and takes the neighbour's quarter by one DPP XOR, ~16
+// VALU, 7 of them 32-bit VOP2 encodings, where gf_muladd2's butterfly is 25 of the
+// 64-bit kind.  Row I/O: the dense kernel already loads a row's low and high dword on
+// lanes 2k and 2k + 1; here that pairing is the placement, so the lane-bit-0 transposes
+// after the loads and before the stores are gone, a lane loads its plane's dword of 4
+// rows (dense_lane_off) and stores 4 halves.  Layer 0 runs inside a word: both lanes of
+// a pair build the rows' 2-element words and run the 2-element butterfly (split_layer0).
+// Regions, slots, counted waits and the order of the fills are the dense kernel's; the
+// tables come from the split images (rs_stage_map.hpp SplitImage), which are in fill
+// order: a DMA lane's source is the image's base + 16 * its position.
+#define RS_MONO_SPLIT_FORM 1  // (tools/mono_probe.hip: this source has the split form)
+constexpr int kSplitL = 10, kSplitLR = 1, kSplitPK = 2 | 4;  // (FLOW | PAIR)
+
+// Table source: the lane's plane's half (10 words) of a staged slot; `ts` holds the
+// regions' addresses + that half's offset
+template <int L, int LR, int PK>
+struct PlaneTabs {
+    LdsTabs<L, LR, PK, 2> ts;
+    template <int, int, typename S, int I, int PH>
+    __device__ __forceinline__ void get(int x, uint32_t row, uint32_t (&t)[10]) const {
+        const uint2 *p = reinterpret_cast<const uint2 *>(ts.template tab<0, 0, S, I, PH>(x, row));
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            const uint2 v = p[q];
+            t[2 * q] = v.x, t[2 * q + 1] = v.y;
+        }
+    }
+};
+
+// Layer 0 of the rows (engine_naive.rs:96-100 IFFT / :64-68 FFT) between the two rows of
+// each pair row, placement maps[I] of S: the neighbour's plane comes by one DPP move, the
+// rows' 2-element words [lo0 lo1 hi0 hi1] are put together, the 2-element butterfly runs
+// on the staged layer-0 table of the pair row (slot sg(q) of the wave's region `priv`),
+// and the lane keeps its own plane of the result.  Both lanes of a pair compute the same.
+template <int L, int LR, typename S, int I, bool FFT>
+__device__ __forceinline__ void split_layer0(Col<L, LR, 1> &c, const uint32_t *priv, uint32_t lane, uint32_t wave) {
+    using G = Stage<L, LR, kSplitPK, 2>;
+    const uint32_t a0 = lane_rows<S, I>(lane, wave);
+    // v_perm_b32 selectors (bytes 0-3: the lane's own word, 4-7: the other operand): row
+    // 2q is bytes 0-1 of both planes, row 2q + 1 bytes 2-3; the own plane goes low on an
+    // even lane and high on an odd one
+    const bool hp = lane & 1u;
+    const uint32_t sel_a = hp ? 0x01000504u : 0x05040100u, sel_b = hp ? 0x03020706u : 0x07060302u;
+    const uint32_t sel_o = hp ? 0x07060302u : 0x05040100u;
+    static_for<0, (1 << LR)>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const uint32_t q = ((a0 | reg_rows<S, I, LR>(i)) & (G::W - 1u)) >> 1;
+        uint32_t t[16];
+        const uint4 *p = reinterpret_cast<const uint4 *>(priv + G::sg(q) * G::SW);
+        static_for<0, 4>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            const uint4 v = p[k];
+            t[4 * k] = v.x, t[4 * k + 1] = v.y, t[4 * k + 2] = v.z, t[4 * k + 3] = v.w;
+        });
+        const uint32_t nb = xor_lane<0>(c.lo[i]);
+        uint32_t a = __builtin_amdgcn_perm(nb, c.lo[i], sel_a);
+        uint32_t b = __builtin_amdgcn_perm(nb, c.lo[i], sel_b);
+        if constexpr (FFT) fft_bfly2(a, b, t);
+        else ifft_bfly2(a, b, t);
+        c.lo[i] = __builtin_amdgcn_perm(b, a, sel_o);
+    });
+}
+
+// DMA fill of POS 16-byte positions at LDS address lds_dst from the image words at src,
+// in order (glds16: lane l of instruction kc fills position 64 kc + l); lanes past the
+// end sit out
+template <uint32_t POS>
+__device__ __forceinline__ void dma_linear(const uint32_t *src, uint32_t lane, uint32_t lds_dst) {
+    const uint32_t off = lane * 16u;
+    static_for<0, int((POS + 63u) / 64u)>([&](auto kc_) {
+        constexpr uint32_t kc = decltype(kc_)::value;
+        if (64u * kc + 63u < POS || lane + 64u * kc < POS) glds16(src + 256u * kc, off, lds_dst + 1024u * kc);
+    });
+}
+
+// Arguments as k_mono_dense's (all preloaded; one stripe: nothing else is read).  img:
+// the split images (SplitImage<10>::kWords words each), imgs = ifft_img | fft_img << 16.
+template <int L_>
+__global__ void __launch_bounds__(1 << (kSplitL - kSplitLR))
+k_mono_split(const uint8_t *src, uint64_t src_stride, uint8_t *dst, uint64_t dst_stride, uint32_t packs,
+             uint32_t packs_per_xcd, const uint32_t *img, uint32_t imgs) {
+    static_assert(L_ == kSplitL, "split encode: 2^10 rows");  // (a template: built where it is launched)
+    constexpr int L = kSplitL, LR = kSplitLR, PK = kSplitPK;
+    using G = Stage<L, LR, PK, 2>;
+    using SI = SplitImage<L>;
+    static_assert(std::is_same_v<typename G::SM, typename SI::SM> && !G::B0 && G::SW == SI::SW &&
+                      G::kWaves == SI::kWaves && G::kShared == 2 * SI::kTop,
+                  "rs_stage_map.hpp SplitImage: the same regions");
+    using SI_ = SeqOf<L, LR, false, PK>;
+    using SF_ = SeqOf<L, LR, true, PK>;
+    static_assert(SI_::v.maps[0].lane[0] == 0 && SF_::v.maps[SF_::v.count].lane[0] == 0 && SI_::v.maps[0].reg[0] == 1,
+                  "pair plan: the plane on lane bit 0, row bit 1 in the register bit at the loads");
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t *plane = lds;
+    const uint32_t b = blockIdx.x;
+    const uint32_t pk = (b & 7u) * packs_per_xcd + (b >> 3);  // (XCD-aware, as mono_body)
+    if (pk >= packs) return;
+    MonoCore A;
+    A.src[0] = RowMap{src, src_stride, 0u, 1u << L};
+    A.dst = RowMap{dst, dst_stride, 0u, 1u << L};
+    const StripeBases sb{src, src, dst};
+    const PackIO io{(pk >> 4) * 64u + (pk & 15u) * 2u, 32u, 2u, false};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t ii = imgs & 0xFFFFu, fi = imgs >> 16;
+    const uint32_t *img_i = img + ii * SI::kWords, *img_f = img + fi * SI::kWords;
+    uint32_t *shared = lds + G::plane_words;
+    uint32_t *priv = shared + G::kShared * G::SW + wave * G::kPriv * G::SW;
+    const uint32_t lds_priv = lds_addr(priv), lds_shared = lds_addr(shared);
+    RS_MSTAMP(0);
+    // every global read is requested first: a lane's plane's dword of its 4 rows (word j:
+    // the lane's first row + j; rows 2q, 2q + 1 of register 0, then of register 1) ...
+    uint32_t w[2 << LR], okm;
+    issue_col<L, LR, PK, 2, -1, false, true>(A, 0u, io, sb, w, okm, lane, wave);
+    // ... the wave's region (phase 1's tables and layer 0's, IFFT image), and the shared
+    // region: the IFFT image's top tables by wave 0, the FFT image's by wave 1
+    dma_linear<SI::kPrivPos>(img_i + SI::priv_off(wave), lane, lds_priv);
+    if (wave < 2)
+        dma_linear<SI::kTopPos>((wave ? img_f : img_i) + SI::top_off(), lane, lds_shared + wave * (16u * SI::kTopPos));
+    RS_MSTAMP(13);
+    Col<L, LR, 1> c;
+    c.m7 = 0x07070707u, c.m3 = 0x03030303u;
+    asm volatile("" : "+s"(c.m7), "+s"(c.m3));  // (field masks in SGPRs: the selectors are 32-bit VOP2)
+    {
+        const uint32_t sel = (io.lo & 2u) ? 0x07060302u : 0x05040100u;  // the half inside its aligned dword
+        static_for<0, (1 << LR)>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            c.lo[i] = __builtin_amdgcn_perm(w[2 * i + 1], w[2 * i], sel);
+        });
+    }
+    // wait 1 (as mono_body's): the DMAs are the wave's newest vector-memory operations
+    dma_wait<0>();
+    RS_MSTAMP(1);
+    split_layer0<L, LR, SI_, 0, false>(c, priv, lane, wave);
+    const uint32_t half = (lane & 1u) * 10u;  // the lane's plane's half of a slot (words)
+    const PlaneTabs<L, LR, PK> ts{LdsTabs<L, LR, PK, 2>{priv + half, shared + half, img_i, img_f}};
+    // phase 3's tables (and the FFT's layer 0's) over phase 1's when phase 1 ends: the
+    // wave's reads of the region have returned (lgkmcnt(0)), the DMAs land behind wait 2
+    auto issue3 = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        dma_linear<SI::kPrivPos>(img_f + SI::priv_off(wave), lane, lds_priv);
+    };
+    run_seq<L, LR, false, RS_MONO_LDS_PF, -1, PK>(ts, c, plane, lane, wave, issue3, true, true, NoHook{}, ii == 0);
+    RS_MSTAMP(5);
+    auto wait3 = [&]() { dma_wait<0>(); };  // wait 2: nothing was issued since issue3
+    run_seq<L, LR, true, RS_MONO_LDS_PF, -1, PK>(ts, c, plane, lane, wave, wait3, true, true, NoHook{}, fi == 0);
+    split_layer0<L, LR, SF_, SF_::v.count, true>(c, priv, lane, wave);
+    RS_MSTAMP(10);
+    {
+        constexpr int I = SF_::v.count;
+        const uint32_t st = uint32_t(dst_stride);
+        const uint32_t voff = dense_lane_off<SF_, I, LR>(lane, st);
+        uint8_t *const ub = dense_base<SF_, I>(dst, wave, st, io.lo);
+        static_for<0, (2 << LR)>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            uint8_t *p = ub + uint64_t(paired_delta<SF_, I, LR>(j) * st) + voff;
+            *reinterpret_cast<uint16_t *>(p) = uint16_t((j & 1) ? c.lo[j >> 1] >> 16 : c.lo[j >> 1]);
+        });
+    }
+    RS_MSTAMP(11);
+}
+std::atomic<uint64_t> g_split_launches{0};
 // RS_MONO_DENSE 0 (A/B builds): no dense instantiations
 #ifndef RS_MONO_DENSE
 #define RS_MONO_DENSE 1
@@ -2945,7 +2959,8 @@ constexpr int mono_lr(int L, bool staged) {
 }
 
 template <int L, int MODE, bool STAGED, bool BATCH = false, bool SPLIT = false, int E = 4>
-hipError_t launch_ls(const MonoArgs &A, hipStream_t s, [[maybe_unused]] bool dense = false) {
+hipError_t launch_ls(const MonoArgs &A, hipStream_t s, [[maybe_unused]] bool dense = false,
+                     [[maybe_unused]] const uint32_t *split_img = nullptr) {
     constexpr int LR = mono_lr(L, STAGED);
     using G = Stage<L, LR, mono_pk(MODE, STAGED, SPLIT), E>;
     size_t lds = STAGED ? size_t(SPLIT ? G::words_split : MODE == kMonoDecode ? G::words_dec : G::words_enc2) * 4
@@ -2964,6 +2979,27 @@ hipError_t launch_ls(const MonoArgs &A, hipStream_t s, [[maybe_unused]] bool den
             const DenseRows ddst{A.dst.base, A.dst.stride, A.dst.row_begin, A.dst.row_end};
             if (dense && mono_dense_ok(L, A.nsrc, dsrc, ddst, A.fmt.full_packs, A.fmt.tail_h, A.fmt.io_bytes,
                                        BATCH ? A.src_bstride[0] : 0, BATCH ? A.dst_bstride : 0)) {
+                // the split form of the dense entry (k_mono_split): 2^10 rows, 2-element
+                // packs, one stripe, where the caller handed its images over
+                if constexpr (L == kSplitL && E == 2 && !BATCH) {
+                    if (split_img) {
+                        static std::atomic<uint64_t> attr_split{0};
+                        const auto fs = &k_mono_split<L>;
+                        if (lds > 65536) {
+                            hipError_t e = lds_attr_once(attr_split, reinterpret_cast<const void *>(fs), int(lds));
+                            if (e != hipSuccess) return e;
+                        }
+                        fs<<<dim3(grid), 1 << (L - LR), lds, s>>>(A.src[0].base, A.src[0].stride,
+                                                                 const_cast<uint8_t *>(A.dst.base), A.dst.stride, A.packs,
+                                                                 A.packs_per_xcd, split_img, A.ifft_img | A.fft_img << 16);
+                        // (a form of the dense entry: counted there too; the records keep the route's name)
+                        g_dense_launches.fetch_add(1, std::memory_order_relaxed);
+                        g_split_launches.fetch_add(1, std::memory_order_relaxed);
+                        snprintf(launch_name_buf(), kLaunchNameBytes, "k_mono<%d, %d, %d, true, false, false, %d>", L, LR,
+                                 MODE, E);
+                        return hipGetLastError();
+                    }
+                }
                 static std::atomic<uint64_t> attr_dense{0};
                 const auto fd = &k_mono_dense<L, LR, MODE, BATCH, E>;
                 if (lds > 65536) {
@@ -3006,7 +3042,7 @@ hipError_t launch_ls(const MonoArgs &A, hipStream_t s, [[maybe_unused]] bool den
 }
 
 template <int L, int MODE, int E>
-hipError_t launch_staged(const MonoArgs &A, hipStream_t s, bool dense) {
+hipError_t launch_staged(const MonoArgs &A, hipStream_t s, bool dense, const uint32_t *split_img) {
     if constexpr (MODE == kMonoDecode && split_l(L)) {
         if (A.split) {
             if (A.stripes > 1) return launch_ls<L, MODE, true, true, true, E>(A, s);
@@ -3014,18 +3050,18 @@ hipError_t launch_staged(const MonoArgs &A, hipStream_t s, bool dense) {
         }
     }
     if (A.stripes > 1) return launch_ls<L, MODE, true, true, false, E>(A, s, dense);
-    return launch_ls<L, MODE, true, false, false, E>(A, s, dense);
+    return launch_ls<L, MODE, true, false, false, E>(A, s, dense, split_img);
 }
 
 // Staged (LDS tables) variant: single-chunk transforms, 2 rows per lane.
 template <int L, int MODE>
-hipError_t launch_l(const MonoArgs &A, hipStream_t s, bool dense) {
+hipError_t launch_l(const MonoArgs &A, hipStream_t s, bool dense, const uint32_t *split_img) {
     // the staged decode evaluates eval_poly itself; the unstaged one reads rowinfo
     if constexpr (staged_l(L)) {
         if (A.chunks == 1) {  // = mono_staged()
             if (MODE == kMonoDecode && !A.fused_eval) return hipErrorInvalidValue;
-            if (A.elems == 2) return launch_staged<L, MODE, 2>(A, s, dense);
-            return launch_staged<L, MODE, 4>(A, s, dense);
+            if (A.elems == 2) return launch_staged<L, MODE, 2>(A, s, dense, split_img);
+            return launch_staged<L, MODE, 4>(A, s, dense, split_img);
         }
     }
     if (A.fused_eval || A.stripes > 1 || A.elems != 4) return hipErrorInvalidValue;
@@ -3046,15 +3082,15 @@ hipError_t launch_l(const MonoArgs &A, hipStream_t s, bool dense) {
 #endif
 
 template <int MODE>
-hipError_t launch_m(int L, const MonoArgs &A, hipStream_t s, bool dense) {
+hipError_t launch_m(int L, const MonoArgs &A, hipStream_t s, bool dense, const uint32_t *split_img) {
     if constexpr (!RS_MONO_HAS_MODE(MODE)) return hipErrorNotSupported;
     switch (L) {
-        case 7: if constexpr (RS_MONO_HAS_L(7)) return launch_l<7, MODE>(A, s, dense); break;
-        case 8: if constexpr (RS_MONO_HAS_L(8)) return launch_l<8, MODE>(A, s, dense); break;
-        case 9: if constexpr (RS_MONO_HAS_L(9)) return launch_l<9, MODE>(A, s, dense); break;
-        case 10: if constexpr (RS_MONO_HAS_L(10)) return launch_l<10, MODE>(A, s, dense); break;
-        case 11: if constexpr (RS_MONO_HAS_L(11)) return launch_l<11, MODE>(A, s, dense); break;
-        case 12: if constexpr (RS_MONO_HAS_L(12)) return launch_l<12, MODE>(A, s, dense); break;
+        case 7: if constexpr (RS_MONO_HAS_L(7)) return launch_l<7, MODE>(A, s, dense, split_img); break;
+        case 8: if constexpr (RS_MONO_HAS_L(8)) return launch_l<8, MODE>(A, s, dense, split_img); break;
+        case 9: if constexpr (RS_MONO_HAS_L(9)) return launch_l<9, MODE>(A, s, dense, split_img); break;
+        case 10: if constexpr (RS_MONO_HAS_L(10)) return launch_l<10, MODE>(A, s, dense, split_img); break;
+        case 11: if constexpr (RS_MONO_HAS_L(11)) return launch_l<11, MODE>(A, s, dense, split_img); break;
+        case 12: if constexpr (RS_MONO_HAS_L(12)) return launch_l<12, MODE>(A, s, dense, split_img); break;
         default: break;
     }
     return hipErrorNotSupported;
@@ -3431,14 +3467,15 @@ bool mono_split(int L) { return split_l(L) && staged_l(L); }
 int mono_rows_log2_per_lane(int L, uint32_t chunks) { return mono_lr(L, mono_staged(L, chunks)); }
 
 uint64_t mono_dense_launches() { return g_dense_launches.load(std::memory_order_relaxed); }
+uint64_t mono_split_launches() { return g_split_launches.load(std::memory_order_relaxed); }
 
-hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t s) {
+hipError_t launch_mono(int mode, int L, const MonoArgs &A, hipStream_t s, const uint32_t *split_img) {
     if (A.packs == 0) return hipSuccess;
     const bool dense = !(mode & kMonoNoDense);
     switch (mode & ~kMonoNoDense) {
-        case kMonoEncodeHigh: return launch_m<kMonoEncodeHigh>(L, A, s, dense);
-        case kMonoEncodeLow: return launch_m<kMonoEncodeLow>(L, A, s, dense);
-        case kMonoDecode: return launch_m<kMonoDecode>(L, A, s, dense);
+        case kMonoEncodeHigh: return launch_m<kMonoEncodeHigh>(L, A, s, dense, split_img);
+        case kMonoEncodeLow: return launch_m<kMonoEncodeLow>(L, A, s, dense, split_img);
+        case kMonoDecode: return launch_m<kMonoDecode>(L, A, s, dense, nullptr);
         default: return hipErrorNotSupported;
     }
 }

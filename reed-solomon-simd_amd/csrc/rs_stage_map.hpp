@@ -10,6 +10,7 @@
 // (tests/test_stage_map_cpu.py) compile the same text.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -174,5 +175,76 @@ struct StageMap {
 // leaves the top placement after layer IW; layer 0 takes turns at 2^11 rows)
 template <int L, int E>
 using EncodeStageMap = StageMap<L, 7, (L > 7 ? 7 : 0), (L >= 11 ? 1 : 0), E>;
+
+// The split encode's images (rs_mono.hip k_mono_split: the two byte planes of a pair
+// row on neighbouring lanes).  Regions, slots and the Gray swizzle are EncodeStageMap<L, 2>'s;
+// the contents differ: layer 0's tables stay 2-element tables (16 words + padding), the
+// layers above are 4-element tables (20 words, rs_gf.hpp gf_muladd4: rows 2q and 2q + 1
+// share every twiddle above row bit 0), each as the two planes' halves: slot words 0-9
+// the low-plane lane's (table words 0-9: own quarter, then the neighbour's), slot words
+// 10-19 the high-plane lane's (table words 15-19, then 10-14: own quarter first again,
+// rs_gf.hpp gf_half_mul).  One image per skew offset is kept in the order the LDS-DMA
+// fill wants -- wave 0's region, ..., the last wave's, then the 2^(L-IW) - 1 tables of
+// layers IW..L-1 as the shared region holds them -- so a fill position's source is the
+// position itself: no inverse map on the device.  The host builds the image from
+// these maps (rs_codec.cpp split_images); tests/split_plan_check.cpp walks them.
+template <int L>
+struct SplitImage {
+    using SM = EncodeStageMap<L, 2>;
+    static_assert(SM::kTop && SM::kPriv == SM::W - 1 && SM::kShI == SM::kShF && SM::kP3 == SM::kUp,
+                  "split encode: wave bits, no layer-0 turns, both transforms' top tables alike");
+    static constexpr uint32_t SW = 4u * SM::SPC;          // words per slot
+    static constexpr uint32_t kWaves = SM::n / SM::W;
+    static constexpr uint32_t kPrivWords = SM::kPriv * SW;  // a wave region
+    static constexpr uint32_t kTop = SM::kShI;            // tables of layers IW..L-1
+    static constexpr uint32_t kWords = (kWaves * SM::kPriv + kTop) * SW;  // one image
+    static RS_SM_FN uint32_t priv_off(uint32_t wave) { return wave * kPrivWords; }  // (words)
+    static RS_SM_FN uint32_t top_off() { return kWaves * kPrivWords; }
+    // 16-byte positions of a wave region's fill, of one transform's part of the shared region
+    static constexpr uint32_t kPrivPos = SM::kPriv * SM::SPC, kTopPos = kTop * SM::SPC;
+    // A slot word's source: word `word` of table `table` of the layer-ordered image of
+    // `elems`-element tables (rs_device.hpp: slot n - n / 2^b + g); elems = 0: padding
+    struct Word {
+        uint32_t elems, table, word;
+    };
+    // slot word w of a 4-element table -> table word
+    static RS_SM_FN uint32_t plane_word(uint32_t w) { return w < 10u ? w : w < 15u ? w + 5u : w - 5u; }
+    static RS_SM_FN Word priv_word(uint32_t wave, uint32_t slot, uint32_t w) {
+        const uint32_t t = SM::sq_inv(slot, SM::kSeq), b = SM::priv_layer(t);
+        const uint32_t table = SM::priv_table(wave, t, b);
+        if (b == 0) return w < 16u ? Word{2u, table, w} : Word{0u, table, 0u};
+        return Word{4u, table, plane_word(w)};
+    }
+    static RS_SM_FN Word top_word(uint32_t slot, uint32_t w) {
+        return Word{4u, SM::shared_table(SM::sq_inv(slot, uint32_t(L) - SM::kSeq)), plane_word(w)};
+    }
+};
+
+// Skew index of table slot `slot` of image t (skew offset t * 2^L) of a layer-ordered
+// image of a 2^L-row transform (rs_device.hpp: layer b's group g at slot n - n / 2^b + g)
+RS_SM_FN uint32_t image_skew_index(uint32_t L, uint32_t t, uint32_t slot) {
+    const uint32_t n = 1u << L;
+    uint32_t b = 0;
+    while (slot >= n - (n >> (b + 1))) ++b;
+    const uint32_t g = slot - (n - (n >> b));
+    return (g << (b + 1)) + (1u << b) + t * n - 1u;
+}
+
+// Split image t into dst (SplitImage<L>::kWords words) from the perm tables by skew
+// index, perm4: 20 words per table, perm2: 16 (gf_tables.hpp perm_by_skew / perm2_by_skew)
+template <int L>
+inline void split_image_fill(uint32_t *dst, uint32_t t, const uint32_t *perm4, const uint32_t *perm2) {
+    using SI = SplitImage<L>;
+    auto value = [&](const typename SI::Word &s) -> uint32_t {
+        const size_t idx = image_skew_index(uint32_t(L), t, s.table);
+        return s.elems == 4u ? perm4[idx * 20u + s.word] : s.elems == 2u ? perm2[idx * 16u + s.word] : 0u;
+    };
+    for (uint32_t wave = 0; wave < SI::kWaves; ++wave)
+        for (uint32_t slot = 0; slot < SI::SM::kPriv; ++slot)
+            for (uint32_t w = 0; w < SI::SW; ++w)
+                dst[SI::priv_off(wave) + slot * SI::SW + w] = value(SI::priv_word(wave, slot, w));
+    for (uint32_t slot = 0; slot < SI::kTop; ++slot)
+        for (uint32_t w = 0; w < SI::SW; ++w) dst[SI::top_off() + slot * SI::SW + w] = value(SI::top_word(slot, w));
+}
 
 }  // namespace rs

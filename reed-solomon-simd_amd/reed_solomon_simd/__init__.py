@@ -200,8 +200,8 @@ def release_stream_scratch(stream=None, ctx=None) -> None:
 def mono_enable(enable=True, ctx=None) -> None:
     """Column kernel (one workgroup per pack): False = never, True = where fastest (default),
     2 = also multi-chunk and 2^11 / 2^12-row transforms; + 4 no split decode plan, + 8 4-element
-    packs only, + 16 2-element packs everywhere, + 8192 / + 16384 dense encode entry on / off
-    (rs_mono_enable)."""
+    packs only, + 16 2-element packs everywhere, + 8192 / + 16384 dense encode entry on / off,
+    + 32768 / + 65536 its split form on / off (rs_mono_enable)."""
     ctx = ctx or default_context()
     _lib.rs_mono_enable(ctx.handle, int(enable))
 
@@ -212,6 +212,14 @@ _sig("rs_mono_dense_launches", _u64)
 def mono_dense_launches() -> int:
     """Launches of the column kernel's dense encode entry by this process so far."""
     return int(_lib.rs_mono_dense_launches())
+
+
+_sig("rs_mono_split_launches", _u64)
+
+
+def mono_split_launches() -> int:
+    """Launches of the dense entry's split form by this process so far (each also a dense launch)."""
+    return int(_lib.rs_mono_split_launches())
 
 
 def check_device(ctx=None) -> None:

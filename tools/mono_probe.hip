@@ -165,7 +165,23 @@ int main(int argc, char **argv) {
         if (de[0] == '0' && !dec && !halves) mode |= rs::kMonoNoDense;
 #endif
     const int iters = 1000;
+#ifdef RS_MONO_SPLIT_FORM  // RS_MONO_PROBE_SPLIT=1 in the environment: the dense entry's split form (k_mono_split)
+    const uint32_t *d_simg = nullptr;
+    if (const char *sp = getenv("RS_MONO_PROBE_SPLIT"))
+        if (sp[0] == '1' && e2 && n == 1024 && !dec && !halves) {
+            using SI = rs::SplitImage<10>;
+            std::vector<uint32_t> hs(size_t(2) * SI::kWords);
+            for (uint32_t t = 0; t < 2; ++t)
+                rs::split_image_fill<10>(&hs[size_t(t) * SI::kWords], t, T.perm_by_skew.data(), T.perm2_by_skew.data());
+            uint32_t *d;
+            CK(hipMalloc(&d, hs.size() * 4));
+            CK(hipMemcpy(d, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+            d_simg = d;
+        }
+    auto go = [&] { CK(halves ? rs::launch_mono_half(mode, halves, A, 0) : rs::launch_mono(mode, int(L), A, 0, d_simg)); };
+#else
     auto go = [&] { CK(halves ? rs::launch_mono_half(mode, halves, A, 0) : rs::launch_mono(mode, int(L), A, 0)); };
+#endif
     for (int i = 0; i < 20; ++i) go();
     hipEvent_t a, b;
     CK(hipEventCreate(&a));
@@ -186,6 +202,9 @@ int main(int argc, char **argv) {
            A.split ? " split" : "", e2 ? " e2" : "", n, S, ms * 1000 / iters, (unsigned long long)hsh);
 #ifdef RS_MONO_DENSE
     printf("dense entry launches: %llu\n", (unsigned long long)rs::mono_dense_launches());
+#endif
+#ifdef RS_MONO_SPLIT_FORM
+    printf("split form launches: %llu\n", (unsigned long long)rs::mono_split_launches());
 #endif
     {  // floor: an empty kernel with the same grid, block and LDS
         const size_t lds = size_t(rs::Stage<10, 1>::words_dec) * 4;
