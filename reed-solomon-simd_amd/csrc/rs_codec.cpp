@@ -1860,6 +1860,16 @@ void update_launch(hipStream_t s, uint64_t bytes, F &&launch) {
     if (t_prof_ctx) prof_end(s, ev, rs::launch_name_buf(), bytes);
 }
 
+// The log of every element on the device (rs_context::d_log), uploaded by the context's
+// first call that needs it: an update's direct route, a locate's or a degraded locate's table.
+void log_table_dev(rs_context *ctx) {
+    if (!ctx->d_log) {
+        const rs::GfTables &T = rs::tables();
+        check(hipMalloc(&ctx->d_log, T.log.size() * 2));
+        check(hipMemcpy(ctx->d_log, T.log.data(), T.log.size() * 2, hipMemcpyHostToDevice));
+    }
+}
+
 struct UpdateCall {
     uint64_t N, M, S, count, stripes;
     const uint64_t *index;
@@ -1899,11 +1909,7 @@ void update_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
     };
 
     if (count <= std::min(ctx->update_direct_max, kUpdateDirectCap)) {
-        if (!ctx->d_log) {  // the context's first update
-            const rs::GfTables &T = rs::tables();
-            check(hipMalloc(&ctx->d_log, T.log.size() * 2));
-            check(hipMemcpy(ctx->d_log, T.log.data(), T.log.size() * 2, hipMemcpyHostToDevice));
-        }
+        log_table_dev(ctx);
         const std::vector<uint32_t> key(lists.begin(), lists.begin() + count);
         if (!u.coef_valid || u.coef_high != int(high) || u.coef_n != U.N || u.coef_m != U.M || u.coef_index != key) {
             u.coef_valid = false;
@@ -1997,25 +2003,66 @@ void verify_mask(Workspace &ws, const uint8_t *host_mask, uint32_t M, uint32_t n
     *d_list = reinterpret_cast<const uint32_t *>(*d_sel + list_off);
 }
 
+// What the host keeps of a mask of M rows: the span of its selected rows and their
+// number.  No mask selects every row.  (Of stripe b's mask in a *_batch_masks call,
+// nsel = 0: the stripe is left alone -- nothing selected, or a locate skips it.)
+struct StripeSel {
+    uint32_t lo, hi, nsel;
+};
+
+StripeSel stripe_sel(const uint8_t *mask, uint32_t M) {
+    if (!mask) return StripeSel{0, M, M};
+    StripeSel r{M, 0, 0};
+    for (uint32_t j = 0; j < M; ++j)
+        if (mask[j]) r.lo = std::min(r.lo, j), r.hi = j + 1, ++r.nsel;
+    return r;
+}
+
+// The encode's transform: does it run as the staged single-chunk column kernel (one
+// launch for a batch, encode_high / encode_low)?  *L_out: log2 of its rows.
+bool verify_column(rs_context *ctx, bool high, const Geom &g, uint64_t N, uint64_t M, uint32_t *L_out) {
+    const uint32_t n = uint32_t(next_pow2(high ? M : N)), L = ilog2(n);
+    const uint32_t C = uint32_t(((high ? N : M) + n - 1) / n);
+    *L_out = L;
+    return use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+}
+
+// The caller's Geom as that of the unfused encode into scratch: recovery rows of
+// g.stride bytes, V.M of them per stripe.
+Geom scratch_geom(const Geom &g, const VerifyCall &V) {
+    const uint64_t W = g.stride;
+    Geom ge = g;
+    ge.rec_stride = W;
+    ge.orig_bstride = V.orig_bstride;
+    ge.rec_bstride = V.M * W;
+    return ge;
+}
+
+// The compare of `stripes` stripes from stripe b0 on: `want` (scratch rows of g.stride
+// bytes, V.M per stripe) against the caller's recovery matrix, over the row list.
+rs::VerifyRowsArgs verify_rows_args(const Geom &g, const VerifyCall &V, uint64_t b0, const uint8_t *want,
+                                    const uint32_t *rows, uint32_t nrows, uint32_t stripes) {
+    rs::VerifyRowsArgs R;
+    R.want = want, R.want_stride = g.stride, R.want_bstride = V.M * g.stride;
+    R.have = V.d_rec + b0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
+    R.rows = rows, R.nrows = nrows, R.packs = g.packs, R.stripes = stripes;
+    R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
+    R.fmt = g.fmt;
+    return R;
+}
+
 // The caller has checked that the mask selects a row and that stripes > 0.
 void verify_dev(rs_context *ctx, Workspace &ws, bool high, Geom g, const VerifyCall &V, hipStream_t s) {
     const uint32_t M = uint32_t(V.M);
-    uint32_t lo = 0, hi = M, nsel = M;  // the span of the selected rows and their number
-    if (V.mask) {
-        lo = M, hi = 0, nsel = 0;
-        for (uint32_t j = 0; j < M; ++j)
-            if (V.mask[j]) lo = std::min(lo, j), hi = j + 1, ++nsel;
-    }
+    const StripeSel sel = stripe_sel(V.mask, M);
+    const uint32_t lo = sel.lo, hi = sel.hi, nsel = sel.nsel;
     // every flag is defined after the call: zero, then the kernels store the ones
     check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
     const uint8_t *d_sel = nullptr;    // M selection bytes (the fused kernel)
     const uint32_t *d_list = nullptr;  // the nsel selected rows (k_verify_rows)
     if (nsel < M) verify_mask(ws, V.mask, M, nsel, s, &d_sel, &d_list);
-    // the encode's transform: does it run as the staged single-chunk column kernel
-    // (one launch for a batch, encode_high / encode_low)?
-    const uint32_t n = uint32_t(next_pow2(high ? V.M : V.N)), L = ilog2(n);
-    const uint32_t C = uint32_t(((high ? V.N : V.M) + n - 1) / n);
-    const bool column = use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+    uint32_t L = 0;
+    const bool column = verify_column(ctx, high, g, V.N, V.M, &L);
     const uint64_t pack_bytes = uint64_t(g.packs) * 8;
 
     if (column && ctx->verify_fused) {
@@ -2047,21 +2094,13 @@ void verify_dev(rs_context *ctx, Workspace &ws, bool high, Geom g, const VerifyC
     if (!ws.ver) ws.ver.reset(new VerifyWs);
     const uint64_t W = g.stride, group = column ? kMaxBatchStripes : 1;
     uint8_t *enc = static_cast<uint8_t *>(ws.ver->enc.get(std::min<uint64_t>(group, V.stripes) * V.M * W));
-    Geom ge = g;
-    ge.rec_stride = W;
-    ge.orig_bstride = V.orig_bstride;
-    ge.rec_bstride = V.M * W;
+    Geom ge = scratch_geom(g, V);
     for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
         ge.stripes = uint32_t(std::min<uint64_t>(group, V.stripes - b0));
         const uint8_t *o = V.d_orig + b0 * V.orig_bstride;
         if (high) encode_high(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
         else encode_low(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
-        rs::VerifyRowsArgs R;
-        R.want = enc, R.want_stride = W, R.want_bstride = V.M * W;
-        R.have = V.d_rec + b0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
-        R.rows = d_list, R.nrows = nsel, R.packs = g.packs, R.stripes = ge.stripes;
-        R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
-        R.fmt = g.fmt;
+        const rs::VerifyRowsArgs R = verify_rows_args(g, V, b0, enc, d_list, nsel, ge.stripes);
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(R, s); });
     }
 }
@@ -2078,11 +2117,7 @@ const uint16_t *locate_table(rs_context *ctx, Workspace &ws, bool high, uint64_t
     LocateWs &l = *ws.loc;
     if (l.valid && l.high == int(high) && l.n == N && l.m == M) return static_cast<const uint16_t *>(l.logs.p);
     l.valid = false;
-    if (!ctx->d_log) {  // as the context's first update
-        const rs::GfTables &T = rs::tables();
-        check(hipMalloc(&ctx->d_log, T.log.size() * 2));
-        check(hipMemcpy(ctx->d_log, T.log.data(), T.log.size() * 2, hipMemcpyHostToDevice));
-    }
+    log_table_dev(ctx);
     const uint64_t W = 64 * ((std::min<uint64_t>(kLocateSlab, N) + 31) / 32);
     uint8_t *unit = static_cast<uint8_t *>(l.unit.get(N * W));
     uint8_t *coef = static_cast<uint8_t *>(l.coef.get(M * W));
@@ -2115,6 +2150,32 @@ struct HealCall {
     uint8_t *d_action;
 };
 
+// The LocateArgs part of the arguments of a group's locate launches, after the compare
+// R of the same stripes: its matrices, row list and flags, the table `logs` (locate_table
+// / degraded_table) and where the group's located[] and a heal's `differ` words go.
+void locate_fields(rs::LocateArgs &A, const rs::VerifyRowsArgs &R, const VerifyCall &V, rs_context *ctx,
+                   const uint16_t *logs, int32_t *located, uint32_t *differ) {
+    A.want = R.want, A.want_stride = R.want_stride, A.want_bstride = R.want_bstride;
+    A.have = R.have, A.have_stride = R.have_stride, A.have_bstride = R.have_bstride;
+    A.rows = R.rows, A.nsel = R.nrows, A.packs = R.packs, A.stripes = R.stripes;
+    A.N = uint32_t(V.N), A.M = uint32_t(V.M);
+    A.flags = R.flags, A.flag_bstride = R.flag_bstride;
+    A.located = located;
+    A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
+    A.fmt = R.fmt;
+    A.differ = differ;
+}
+
+// The heal's fields of HealArgs, HealMaskArgs or HealRobustArgs (which repeat them
+// without a common base) for the group of stripes from b0 on.
+template <class Args>
+void heal_fields(Args &A, const HealCall *H, const Geom &g, const VerifyCall &V, uint64_t b0) {
+    A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
+    A.rec = H->d_rec + b0 * V.rec_bstride;
+    A.mode = H->mode, A.max_rows = H->max_rows;
+    A.action = H->d_action + b0;
+}
+
 // The caller has checked that the mask selects two rows at least, the shape bound
 // and that stripes > 0.  The unfused verify (verify_dev) with two more launches per
 // group of stripes while the encode is still in scratch.  With a heal, k_heal is a
@@ -2122,29 +2183,21 @@ struct HealCall {
 void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V, hipStream_t s,
                 const HealCall *H = nullptr) {
     const uint32_t M = uint32_t(V.M);
-    uint32_t lo = 0, hi = M, nsel = M;
-    if (V.mask) {
-        lo = M, hi = 0, nsel = 0;
-        for (uint32_t j = 0; j < M; ++j)
-            if (V.mask[j]) lo = std::min(lo, j), hi = j + 1, ++nsel;
-    }
+    const StripeSel sel = stripe_sel(V.mask, M);
+    const uint32_t lo = sel.lo, hi = sel.hi, nsel = sel.nsel;
     const uint16_t *logs = locate_table(ctx, ws, high, V.N, V.M, s);
     check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
     const uint8_t *d_sel = nullptr;
     const uint32_t *d_list = nullptr;
     if (nsel < M) verify_mask(ws, V.mask, M, nsel, s, &d_sel, &d_list);
-    const uint32_t n = uint32_t(next_pow2(high ? V.M : V.N)), L = ilog2(n);
-    const uint32_t C = uint32_t(((high ? V.N : V.M) + n - 1) / n);
-    const bool column = use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+    uint32_t L = 0;
+    const bool column = verify_column(ctx, high, g, V.N, V.M, &L);
     const uint64_t pack_bytes = uint64_t(g.packs) * 8;
 
     if (!ws.ver) ws.ver.reset(new VerifyWs);
     const uint64_t W = g.stride, group = column ? kMaxBatchStripes : 1;
     uint8_t *enc = static_cast<uint8_t *>(ws.ver->enc.get(std::min<uint64_t>(group, V.stripes) * V.M * W));
-    Geom ge = g;
-    ge.rec_stride = W;
-    ge.orig_bstride = V.orig_bstride;
-    ge.rec_bstride = V.M * W;
+    Geom ge = scratch_geom(g, V);
     uint32_t *differ = nullptr;
     if (H) differ = static_cast<uint32_t *>(ws.loc->differ.get(std::min<uint64_t>(group, V.stripes) * 4));
     for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
@@ -2152,32 +2205,16 @@ void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
         const uint8_t *o = V.d_orig + b0 * V.orig_bstride;
         if (high) encode_high(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
         else encode_low(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
-        rs::VerifyRowsArgs R;
-        R.want = enc, R.want_stride = W, R.want_bstride = V.M * W;
-        R.have = V.d_rec + b0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
-        R.rows = d_list, R.nrows = nsel, R.packs = g.packs, R.stripes = ge.stripes;
-        R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
-        R.fmt = g.fmt;
+        const rs::VerifyRowsArgs R = verify_rows_args(g, V, b0, enc, d_list, nsel, ge.stripes);
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(R, s); });
         rs::HealArgs A;  // the locate's kernels take its LocateArgs
-        A.want = R.want, A.want_stride = W, A.want_bstride = R.want_bstride;
-        A.have = R.have, A.have_stride = R.have_stride, A.have_bstride = R.have_bstride;
-        A.rows = d_list, A.nsel = nsel, A.packs = g.packs, A.stripes = ge.stripes;
-        A.N = uint32_t(V.N), A.M = M;
-        A.flags = R.flags, A.flag_bstride = V.M;
-        A.located = V.d_located + b0;
-        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
-        A.fmt = g.fmt;
+        locate_fields(A, R, V, ctx, logs, V.d_located + b0, differ);
         // find: the flags and one word per stripe; a stripe with a candidate reads up to
         // two rows and two table rows more.  confirm: as the compare, where it runs at all
-        A.differ = differ;
         update_launch(s, (V.M + 4) * uint64_t(ge.stripes), [&] { return rs::launch_locate_find(A, s); });
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_locate_confirm(A, s); });
         if (!H) continue;
-        A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
-        A.rec = H->d_rec + b0 * V.rec_bstride;
-        A.mode = H->mode, A.max_rows = H->max_rows;
-        A.action = H->d_action + b0;
+        heal_fields(A, H, g, V, b0);
         // a stripe with nothing to heal costs a word; a located one three rows, a ROWS one
         // two per rewritten row
         update_launch(s, 5 * uint64_t(ge.stripes), [&] { return rs::launch_heal(A, s); });
@@ -2185,32 +2222,12 @@ void locate_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const 
 }
 
 // ---- verify and locate with a mask per stripe (rs_*_device_batch_masks) ----
-// What the host keeps of stripe b's mask: the span of its selected rows and their
-// number (nsel = 0: the stripe is left alone -- nothing selected, or a locate skips it).
-struct StripeSel {
-    uint32_t lo, hi, nsel;
-};
-
-StripeSel stripe_sel(const uint8_t *mask, uint32_t M) {
-    StripeSel r{M, 0, 0};
-    for (uint32_t j = 0; j < M; ++j)
-        if (mask[j]) r.lo = std::min(r.lo, j), r.hi = j + 1, ++r.nsel;
-    return r;
-}
-
-// The union span and the largest count of stripes [b0, b1).
+// The union span and the largest count of stripes [b0, b1) (StripeSel: above verify_dev).
 StripeSel union_sel(const std::vector<StripeSel> &sel, uint64_t b0, uint64_t b1, uint32_t M) {
     StripeSel u{M, 0, 0};
     for (uint64_t b = b0; b < b1; ++b)
         if (sel[b].nsel) u.lo = std::min(u.lo, sel[b].lo), u.hi = std::max(u.hi, sel[b].hi), u.nsel = std::max(u.nsel, sel[b].nsel);
     return u;
-}
-
-bool verify_column(rs_context *ctx, bool high, const Geom &g, uint64_t N, uint64_t M, uint32_t *L_out) {
-    const uint32_t n = uint32_t(next_pow2(high ? M : N)), L = ilog2(n);
-    const uint32_t C = uint32_t(((high ? N : M) + n - 1) / n);
-    *L_out = L;
-    return use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
 }
 
 // The fused route: the stripes' selection bytes and first-row words go through the
@@ -2302,10 +2319,7 @@ void masks_unfused(rs_context *ctx, Workspace &ws, bool high, const Geom &g, con
     const uint64_t pack_bytes = uint64_t(g.packs) * 8;
     const uint64_t W = g.stride, group = column ? kMaxBatchStripes : 1;
     uint8_t *enc = static_cast<uint8_t *>(v.enc.get(std::min<uint64_t>(group, V.stripes) * V.M * W));
-    Geom ge = g;
-    ge.rec_stride = W;
-    ge.orig_bstride = V.orig_bstride;
-    ge.rec_bstride = V.M * W;
+    Geom ge = scratch_geom(g, V);
     uint32_t *differ = nullptr;  // (the caller's locate_table has made ws.loc)
     if (H) differ = static_cast<uint32_t *>(ws.loc->differ.get(std::min<uint64_t>(group, V.stripes) * 4));
     for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
@@ -2324,38 +2338,25 @@ void masks_unfused(rs_context *ctx, Workspace &ws, bool high, const Geom &g, con
             if (high) encode_high(ctx, ws, ge, V.N, V.M, o, want, s, u.lo, u.hi);
             else encode_low(ctx, ws, ge, V.N, V.M, o, want, s, u.lo, u.hi);
             rs::VerifyRowsMaskArgs R;
-            R.want = want, R.want_stride = W, R.want_bstride = V.M * W;
-            R.have = V.d_rec + r0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
-            R.rows = d_lists + r0 * M, R.list_stride = M, R.counts = d_counts + r0;
-            R.nrows = u.nsel, R.packs = g.packs, R.stripes = ge.stripes;
-            R.flags = V.d_flags + r0 * V.M, R.flag_bstride = V.M;
-            R.fmt = g.fmt;
+            static_cast<rs::VerifyRowsArgs &>(R) = verify_rows_args(g, V, r0, want, d_lists + r0 * M, u.nsel, ge.stripes);
+            R.list_stride = M, R.counts = d_counts + r0;
             update_launch(s, 2 * uint64_t(u.nsel) * pack_bytes * ge.stripes,
                           [&] { return rs::launch_verify_rows_masks(R, s); });
         }
         if (!d_located) continue;
-        // one find and one confirm for the group, as the plain locate's
+        // one find and one confirm for the group, as the plain locate's: over the whole
+        // group's scratch, lists and flags, whatever runs the compares went in
         const StripeSel u = union_sel(sel, b0, b1, M);
         rs::HealMaskArgs A;  // the locate's kernels take its LocateMaskArgs
-        A.want = enc, A.want_stride = W, A.want_bstride = V.M * W;
-        A.have = V.d_rec + b0 * V.rec_bstride, A.have_stride = g.rec(), A.have_bstride = V.rec_bstride;
-        A.rows = d_lists + b0 * M, A.list_stride = M, A.counts = d_counts + b0;
-        A.nsel = u.nsel, A.packs = g.packs, A.stripes = uint32_t(b1 - b0);
-        A.N = uint32_t(V.N), A.M = M;
-        A.flags = V.d_flags + b0 * V.M, A.flag_bstride = V.M;
-        A.located = d_located + b0;
-        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
-        A.fmt = g.fmt;
-        A.differ = differ;
+        locate_fields(A, verify_rows_args(g, V, b0, enc, d_lists + b0 * M, u.nsel, uint32_t(b1 - b0)), V, ctx, logs,
+                      d_located + b0, differ);
+        A.list_stride = M, A.counts = d_counts + b0;
         update_launch(s, (V.M + 4) * uint64_t(A.stripes), [&] { return rs::launch_locate_find_masks(A, s); });
         if (u.nsel < 2) continue;  // every stripe of the group is skipped (a heal's d_action: the caller's memset)
         update_launch(s, 2 * uint64_t(u.nsel) * pack_bytes * A.stripes,
                       [&] { return rs::launch_locate_confirm_masks(A, s); });
         if (!H) continue;
-        A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
-        A.rec = H->d_rec + b0 * V.rec_bstride;
-        A.mode = H->mode, A.max_rows = H->max_rows;
-        A.action = H->d_action + b0;
+        heal_fields(A, H, g, V, b0);
         // as locate_dev's k_heal: a stripe with nothing to heal costs a word
         update_launch(s, 5 * uint64_t(A.stripes), [&] { return rs::launch_heal_masks(A, s); });
     }
@@ -2376,12 +2377,8 @@ struct RobustCall {
 void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const LocateCall &V,
                        const RobustCall &R, hipStream_t s, const HealCall *H = nullptr) {
     const uint32_t M = uint32_t(V.M), t = R.max_outliers;
-    uint32_t lo = 0, hi = M, nsel = M;
-    if (V.mask) {
-        lo = M, hi = 0, nsel = 0;
-        for (uint32_t j = 0; j < M; ++j)
-            if (V.mask[j]) lo = std::min(lo, j), hi = j + 1, ++nsel;
-    }
+    const StripeSel sel = stripe_sel(V.mask, M);
+    const uint32_t lo = sel.lo, hi = sel.hi, nsel = sel.nsel;
     const uint16_t *logs = locate_table(ctx, ws, high, V.N, V.M, s);
     // every flag and every outlier byte is defined after the call: zero, then the kernels store the ones
     check(hipMemsetAsync(V.d_flags, 0, V.stripes * V.M, s));
@@ -2389,9 +2386,8 @@ void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g,
     const uint8_t *d_sel = nullptr;
     const uint32_t *d_list = nullptr;
     if (nsel < M) verify_mask(ws, V.mask, M, nsel, s, &d_sel, &d_list);
-    const uint32_t n = uint32_t(next_pow2(high ? V.M : V.N)), L = ilog2(n);
-    const uint32_t C = uint32_t(((high ? V.N : V.M) + n - 1) / n);
-    const bool column = use_mono(ctx, L, g, C) && rs::mono_staged(int(L), C);
+    uint32_t L = 0;
+    const bool column = verify_column(ctx, high, g, V.N, V.M, &L);
     const uint64_t pack_bytes = uint64_t(g.packs) * 8;
 
     if (!ws.ver) ws.ver.reset(new VerifyWs);
@@ -2401,31 +2397,16 @@ void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g,
     constexpr uint64_t kCands = rs::kRobustMaxOutliers + 1;
     const uint64_t cand_bytes = held * kCands * 4, vote_bstride = uint64_t(t + 1) * V.M;
     uint8_t *scratch = static_cast<uint8_t *>(ws.loc->robust.get(cand_bytes + held * vote_bstride));
-    Geom ge = g;
-    ge.rec_stride = W;
-    ge.orig_bstride = V.orig_bstride;
-    ge.rec_bstride = V.M * W;
+    Geom ge = scratch_geom(g, V);
     for (uint64_t b0 = 0; b0 < V.stripes; b0 += group) {
         ge.stripes = uint32_t(std::min<uint64_t>(group, V.stripes - b0));
         const uint8_t *o = V.d_orig + b0 * V.orig_bstride;
         if (high) encode_high(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
         else encode_low(ctx, ws, ge, V.N, V.M, o, enc, s, lo, hi);
-        rs::VerifyRowsArgs Q;
-        Q.want = enc, Q.want_stride = W, Q.want_bstride = V.M * W;
-        Q.have = V.d_rec + b0 * V.rec_bstride, Q.have_stride = g.rec(), Q.have_bstride = V.rec_bstride;
-        Q.rows = d_list, Q.nrows = nsel, Q.packs = g.packs, Q.stripes = ge.stripes;
-        Q.flags = V.d_flags + b0 * V.M, Q.flag_bstride = V.M;
-        Q.fmt = g.fmt;
+        const rs::VerifyRowsArgs Q = verify_rows_args(g, V, b0, enc, d_list, nsel, ge.stripes);
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_verify_rows(Q, s); });
         rs::HealRobustArgs A;  // the robust locate's kernels take its RobustArgs
-        A.want = Q.want, A.want_stride = W, A.want_bstride = Q.want_bstride;
-        A.have = Q.have, A.have_stride = Q.have_stride, A.have_bstride = Q.have_bstride;
-        A.rows = d_list, A.nsel = nsel, A.packs = g.packs, A.stripes = ge.stripes;
-        A.N = uint32_t(V.N), A.M = M;
-        A.flags = Q.flags, A.flag_bstride = V.M;
-        A.located = V.d_located + b0;
-        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
-        A.fmt = g.fmt;
+        locate_fields(A, Q, V, ctx, logs, V.d_located + b0, nullptr);
         A.t = t;
         A.cand = reinterpret_cast<int32_t *>(scratch);
         A.votes = scratch + cand_bytes, A.vote_bstride = vote_bstride;
@@ -2437,10 +2418,7 @@ void locate_robust_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g,
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * ge.stripes, [&] { return rs::launch_locate_count(A, s); });
         update_launch(s, 4 * (t + 1) * uint64_t(ge.stripes), [&] { return rs::launch_locate_decide(A, s); });
         if (!H) continue;
-        A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
-        A.rec = H->d_rec + b0 * V.rec_bstride;
-        A.mode = H->mode, A.max_rows = H->max_rows;
-        A.action = H->d_action + b0;
+        heal_fields(A, H, g, V, b0);
         // a stripe with nothing to heal costs a word; a located one three rows and two per
         // outlier row, a ROWS one two per rewritten row
         update_launch(s, 5 * uint64_t(ge.stripes), [&] { return rs::launch_heal_robust(A, s); });
@@ -2506,11 +2484,7 @@ const uint16_t *degraded_table(rs_context *ctx, Workspace &ws, bool high, uint64
         return static_cast<const uint16_t *>(d.logs.p);
     }
     d.valid = d.u_valid = false;
-    if (!ctx->d_log) {  // as the context's first update
-        const rs::GfTables &T = rs::tables();
-        check(hipMalloc(&ctx->d_log, T.log.size() * 2));
-        check(hipMemcpy(ctx->d_log, T.log.data(), T.log.size() * 2, hipMemcpyHostToDevice));
-    }
+    log_table_dev(ctx);
     degraded_lists(d, N, present, C, s, d_map, d_check);
     const uint64_t W = 64 * ((std::min<uint64_t>(kLocateSlab, N) + 31) / 32);
     uint8_t *unit = static_cast<uint8_t *>(d.unit.get((N + M) * W)), *unit_rec = unit + N * W;
@@ -2593,30 +2567,14 @@ void locate_degraded_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &
         repair_dev(ctx, ws, high, gr, V.N, V.M, V.d_orig + b0 * V.orig_bstride, C.present,
                    V.d_rec + b0 * V.rec_bstride, ref_mask.data(),
                    C.d_restored ? C.d_restored + b0 * C.restored_bstride : full, want, s);
-        rs::VerifyRowsArgs R;
-        R.want = want, R.want_stride = W, R.want_bstride = V.M * W;
-        R.have = V.d_rec + b0 * V.rec_bstride, R.have_stride = g.rec(), R.have_bstride = V.rec_bstride;
-        R.rows = d_check, R.nrows = nsel, R.packs = g.packs, R.stripes = gr.stripes;
-        R.flags = V.d_flags + b0 * V.M, R.flag_bstride = V.M;
-        R.fmt = g.fmt;
+        const rs::VerifyRowsArgs R = verify_rows_args(g, V, b0, want, d_check, nsel, gr.stripes);
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * gr.stripes, [&] { return rs::launch_verify_rows(R, s); });
         rs::HealDegradedArgs A;  // the locate's kernels take its LocateArgs
-        A.want = R.want, A.want_stride = W, A.want_bstride = R.want_bstride;
-        A.have = R.have, A.have_stride = R.have_stride, A.have_bstride = R.have_bstride;
-        A.rows = d_check, A.nsel = nsel, A.packs = g.packs, A.stripes = gr.stripes;
-        A.N = uint32_t(V.N), A.M = M;
-        A.flags = R.flags, A.flag_bstride = V.M;
-        A.located = V.d_located + b0;
-        A.logs = logs, A.log_table = ctx->d_log, A.lut = ctx->d_lut;
-        A.fmt = g.fmt;
-        A.differ = differ;
+        locate_fields(A, R, V, ctx, logs, V.d_located + b0, differ);
         update_launch(s, (V.M + 4) * uint64_t(gr.stripes), [&] { return rs::launch_locate_find(A, s); });
         update_launch(s, 2 * uint64_t(nsel) * pack_bytes * gr.stripes, [&] { return rs::launch_locate_confirm(A, s); });
         if (H) {
-            A.orig = H->d_orig + b0 * V.orig_bstride, A.orig_stride = g.orig(), A.orig_bstride = V.orig_bstride;
-            A.rec = H->d_rec + b0 * V.rec_bstride;
-            A.mode = H->mode, A.max_rows = H->max_rows;
-            A.action = H->d_action + b0;
+            heal_fields(A, H, g, V, b0);
             A.map = d_map, A.miss = d_check + nsel, A.m = uint32_t(C.ref.size());
             A.logu = static_cast<const uint16_t *>(d.logu.p);
             A.restored = C.d_restored + b0 * C.restored_bstride;
@@ -2995,6 +2953,8 @@ uint64_t rs_decoder_work_count(rs_rate rate, uint64_t N, uint64_t M) {
     return high ? next_pow2(next_pow2(M) + N) : next_pow2(next_pow2(N) + M);
 }
 
+}  // extern "C"
+
 // ---- device-resident ------------------------------------------------------
 
 namespace {
@@ -3002,7 +2962,112 @@ namespace {
 // unaligned matrices go byte by byte (ShardFormat::io_bytes)
 bool stride_ok(uint64_t stride, uint64_t S) { return stride == 0 || stride >= S; }
 bool ptr_ok(const void *p) { return p != nullptr; }
+
+// The rows a mask of M bytes selects; no mask: all of them.
+uint64_t count_selected(const uint8_t *mask, uint64_t M) {
+    if (!mask) return M;
+    uint64_t n = 0;
+    for (uint64_t j = 0; j < M; ++j) n += mask[j] != 0;
+    return n;
+}
+bool heal_mode_ok(uint32_t mode) { return mode && !(mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY)); }
+// the locate's table: original_count and the coefficients it holds
+bool locate_shape_ok(uint64_t N, uint64_t M) {
+    return N <= RS_LOCATE_MAX_ORIGINALS && N * M <= RS_LOCATE_MAX_COEFFICIENTS;
+}
+rs_status not_enough_shards(rs_error *err, uint64_t N, uint64_t have_o, uint64_t have_r) {
+    set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
+    if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = have_r;
+    return RS_ERR_NOT_ENOUGH_SHARDS;
+}
+
+// The byte-wise layout forced on the matrices of shards of S bytes: a batch whose
+// stripe strides are no multiple of 4 leaves later stripes unaligned (the row strides
+// and the base pointers: device_geom).
+void force_bytes(Geom &g, uint64_t S) {
+    g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+}
+
+// One call on the caller's stream: f(workspace, stream) under the context's mutex, on
+// its device, with its kernel timing and the stream's workspace; RS_OK unless f throws.
+template <typename F>
+rs_status device_call(rs_context *ctx, void *stream, rs_error *err, F &&f) {
+    return guarded(err, [&]() -> rs_status {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        ProfScope prof(ctx);
+        auto s = static_cast<hipStream_t>(stream);
+        StreamWs sw(ctx, s);
+        f(sw.w, s);
+        return set_err(err, RS_OK);
+    });
+}
+
+// A shard matrix as the ABI passes it: row stride and stripe stride in bytes, 0 = dense.
+struct Matrix {
+    const void *d;
+    uint64_t stride, stripe_stride;
+};
+
+// The Geom and the call of a scrub entry point (rs_verify_*, rs_locate_*, rs_heal_*):
+// stripe strides of 0 are the matrices', and a batch with one that is no multiple of 4
+// goes byte by byte.  d_located: nullptr for the verify calls (V as a VerifyCall).
+// restored: the degraded calls' third matrix; where its d is nullptr the restored
+// originals go to scratch, like the completed stripe's recovery rows -- rows of whole
+// 64-byte blocks, so neither stride of the scratch forces the byte-wise path.
+struct ScrubCall {
+    Geom g;
+    LocateCall V;
+    uint64_t restored_bstride;  // (restored->d given, else 0)
+};
+ScrubCall scrub_call(uint64_t N, uint64_t M, uint64_t S, uint64_t stripes, const Matrix &orig, const Matrix &rec,
+                     const uint8_t *recovery_check, uint8_t *d_mismatch, int32_t *d_located = nullptr,
+                     const Matrix *restored = nullptr) {
+    const uint64_t W = round_up(S, 64);
+    Geom g = !restored     ? device_geom(S, orig.stride, rec.stride, 0, {orig.d, rec.d})
+             : restored->d ? device_geom(S, orig.stride, rec.stride, restored->stride, {orig.d, rec.d, restored->d}, W)
+                           : device_geom(S, orig.stride, rec.stride, W, {orig.d, rec.d}, W);
+    const LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(orig.d), static_cast<const uint8_t *>(rec.d),
+                        orig.stripe_stride ? orig.stripe_stride : N * g.orig(),
+                        rec.stripe_stride ? rec.stripe_stride : M * g.rec(), recovery_check, d_mismatch},
+                       d_located};
+    uint64_t restored_b = 0;
+    if (restored && restored->d) restored_b = restored->stripe_stride ? restored->stripe_stride : N * g.out();
+    if (stripes > 1 && (V.orig_bstride | V.rec_bstride | restored_b) % 4) force_bytes(g, S);
+    return ScrubCall{g, V, restored_b};
+}
+
+// Every stripe's mask of a *_batch_masks locate or heal, in stripe order, before any
+// device work: sel[b] and, where given, stripe_status[b].  A stripe that selects fewer
+// than `need` rows is skipped (none of its rows is read or written) -- or, with no
+// status array, refuses the whole call: false, with RS_ERR_INVALID_ARGUMENT and
+// err->index = the stripe in *err.
+bool scan_stripe_masks(const uint8_t *recovery_check, uint64_t M, uint64_t stripes, uint32_t need,
+                       uint8_t *stripe_status, std::vector<StripeSel> &sel, rs_error *err) {
+    sel.resize(stripes);
+    for (uint64_t b = 0; b < stripes; ++b) {
+        sel[b] = stripe_sel(recovery_check + b * M, uint32_t(M));
+        if (stripe_status) stripe_status[b] = sel[b].nsel < need ? RS_ERR_INVALID_ARGUMENT : RS_OK;
+        if (sel[b].nsel >= need) continue;
+        if (!stripe_status) {
+            set_err(err, RS_ERR_INVALID_ARGUMENT);
+            if (err) err->index = b;
+            return false;
+        }
+        sel[b] = StripeSel{uint32_t(M), 0, 0};
+    }
+    return true;
+}
+
+// The selected rows in order: the first `missing` are the reference rows R, the rest
+// the check rows K (DegradedCall).
+void split_rows(const uint8_t *recovery_check, uint64_t M, uint64_t missing, DegradedCall &C) {
+    for (uint64_t j = 0; j < M; ++j)
+        if (!recovery_check || recovery_check[j]) (C.ref.size() < missing ? C.ref : C.check).push_back(uint32_t(j));
+}
 }  // namespace
+
+extern "C" {
 
 rs_status rs_encode_device_strided(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
                                    const void *d_orig, uint64_t orig_stride, void *d_rec, uint64_t rec_stride,
@@ -3041,26 +3106,20 @@ rs_status rs_encode_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
     const uint64_t orig_b = orig_stripe_stride ? orig_stripe_stride : N * (orig_stride ? orig_stride : S);
     const uint64_t rec_b = rec_stripe_stride ? rec_stripe_stride : M * (rec_stride ? rec_stride : S);
     if (stripes == 0) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
+    return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
         Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        if ((orig_b | rec_b) % 4) g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        if ((orig_b | rec_b) % 4) force_bytes(g, S);
         g.orig_bstride = orig_b;
         g.rec_bstride = rec_b;
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
         for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
             g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
             const uint8_t *o = static_cast<const uint8_t *>(d_orig) + b0 * orig_b;
             uint8_t *r = static_cast<uint8_t *>(d_rec) + b0 * rec_b;
             if (high)
-                encode_high(ctx, sw.w, g, N, M, o, r, s);
+                encode_high(ctx, ws, g, N, M, o, r, s);
             else
-                encode_low(ctx, sw.w, g, N, M, o, r, s);
+                encode_low(ctx, ws, g, N, M, o, r, s);
         }
-        return set_err(err, RS_OK);
     });
 }
 
@@ -3189,14 +3248,8 @@ rs_status rs_decode_host(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, 
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
     const int high = resolve(rate, N, M, S, err);
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
-    uint64_t have_o = 0, have_r = 0;
-    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
-    for (uint64_t i = 0; i < M; ++i) have_r += rec_present[i] != 0;
-    if (have_o + have_r < N) {
-        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = have_r;
-        return RS_ERR_NOT_ENOUGH_SHARDS;
-    }
+    const uint64_t have_o = count_selected(orig_present, N), have_r = count_selected(rec_present, M);
+    if (have_o + have_r < N) return not_enough_shards(err, N, have_o, have_r);
     if (have_o == N) return set_err(err, RS_OK);
     return guarded(err, [&]() -> rs_status {
         std::lock_guard<std::mutex> lock(ctx->mu);
@@ -3238,25 +3291,13 @@ rs_status rs_decode_device_strided(rs_context *ctx, rs_rate rate, uint64_t N, ui
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S))
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t have_o = 0, have_r = 0;
-    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
-    for (uint64_t i = 0; i < M; ++i) have_r += rec_present[i] != 0;
-    if (have_o + have_r < N) {
-        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = have_r;
-        return RS_ERR_NOT_ENOUGH_SHARDS;
-    }
+    const uint64_t have_o = count_selected(orig_present, N), have_r = count_selected(rec_present, M);
+    if (have_o + have_r < N) return not_enough_shards(err, N, have_o, have_r);
     if (have_o == N) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
+    return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
         const Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored});
-        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
-        decode_dev(ctx, sw.w, high, g, N, M, static_cast<const uint8_t *>(d_orig), orig_present,
-                   static_cast<const uint8_t *>(d_rec), rec_present, static_cast<uint8_t *>(d_restored),
-                   static_cast<hipStream_t>(stream));
-        return set_err(err, RS_OK);
+        decode_dev(ctx, ws, high, g, N, M, static_cast<const uint8_t *>(d_orig), orig_present,
+                   static_cast<const uint8_t *>(d_rec), rec_present, static_cast<uint8_t *>(d_restored), s);
     });
 }
 
@@ -3279,34 +3320,21 @@ rs_status rs_decode_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S))
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t have_o = 0, have_r = 0;
-    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
-    for (uint64_t i = 0; i < M; ++i) have_r += rec_present[i] != 0;
-    if (have_o + have_r < N) {
-        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = have_r;
-        return RS_ERR_NOT_ENOUGH_SHARDS;
-    }
+    const uint64_t have_o = count_selected(orig_present, N), have_r = count_selected(rec_present, M);
+    if (have_o + have_r < N) return not_enough_shards(err, N, have_o, have_r);
     if (have_o == N || stripes == 0) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
+    return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
         Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored});
         g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
         g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
         g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
-        if ((g.orig_bstride | g.rec_bstride | g.out_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
+        if ((g.orig_bstride | g.rec_bstride | g.out_bstride) % 4) force_bytes(g, S);
         for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
             g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
-            decode_dev(ctx, sw.w, high, g, N, M,
-                       static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
+            decode_dev(ctx, ws, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
                        orig_present, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride, rec_present,
-                       static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride, static_cast<hipStream_t>(stream));
+                       static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride, s);
         }
-        return set_err(err, RS_OK);
     });
 }
 
@@ -3327,40 +3355,27 @@ rs_status rs_repair_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S) ||
         !stride_ok(recovery_out_stride, S))
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t have_o = 0, have_r = 0;
-    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
-    for (uint64_t i = 0; i < M; ++i) have_r += rec_present[i] != 0;
-    if (have_o + have_r < N) {
-        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = have_r;
-        return RS_ERR_NOT_ENOUGH_SHARDS;
-    }
+    const uint64_t have_o = count_selected(orig_present, N), have_r = count_selected(rec_present, M);
+    if (have_o + have_r < N) return not_enough_shards(err, N, have_o, have_r);
     // nothing missing: nothing launched, nothing written, the context not touched.
     // Missing recovery shards alone still run (the decode returns here for them).
     if ((have_o == N && have_r == M) || stripes == 0) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
+    return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
         Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored, d_recovery_out},
                              recovery_out_stride);
         g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
         g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
         g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
         g.out2_bstride = recovery_out_stripe_stride ? recovery_out_stripe_stride : M * g.out2();
-        if (stripes > 1 && (g.orig_bstride | g.rec_bstride | g.out_bstride | g.out2_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
+        if (stripes > 1 && (g.orig_bstride | g.rec_bstride | g.out_bstride | g.out2_bstride) % 4) force_bytes(g, S);
         // (the route of the pattern -- narrowed encode or the decode's kernels: repair_dev)
         for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
             g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
-            repair_dev(ctx, sw.w, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
+            repair_dev(ctx, ws, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
                        orig_present, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride, rec_present,
                        static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
-                       static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride,
-                       static_cast<hipStream_t>(stream));
+                       static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride, s);
         }
-        return set_err(err, RS_OK);
     });
 }
 
@@ -3400,10 +3415,7 @@ rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
         std::vector<uint8_t> skip(stripes, 0);
         bool work = false;
         for (uint64_t b = 0; b < stripes; ++b) {
-            const uint8_t *op = orig_present + b * N, *rp = rec_present + b * M;
-            uint64_t have_o = 0, have_r = 0;
-            for (uint64_t i = 0; i < N; ++i) have_o += op[i] != 0;
-            for (uint64_t i = 0; i < M; ++i) have_r += rp[i] != 0;
+            const uint64_t have_o = count_selected(orig_present + b * N, N), have_r = count_selected(rec_present + b * M, M);
             if (stripe_status) stripe_status[b] = RS_OK;
             if (have_o + have_r < N) {
                 if (stripe_status) {
@@ -3411,36 +3423,28 @@ rs_status rs_decode_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
                     skip[b] = 2;
                     continue;
                 }
-                set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-                if (err) {
-                    err->original_count = N, err->original_received_count = have_o;
-                    err->recovery_received_count = have_r;
-                    err->index = b;  // the stripe (extension: the reference variant leaves index unused)
-                }
+                not_enough_shards(err, N, have_o, have_r);
+                if (err) err->index = b;  // the stripe (extension: the reference variant leaves index unused)
                 return RS_ERR_NOT_ENOUGH_SHARDS;
             }
             if (have_o == N) skip[b] = 1;
             else work = true;
         }
         if (!work) return set_err(err, RS_OK);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored});
-        g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
-        if ((g.orig_bstride | g.rec_bstride | g.out_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
-        for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
-            g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
-            decode_masks_dev(ctx, sw.w, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
-                             orig_present + b0 * N, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride,
-                             rec_present + b0 * M, static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
-                             skip.data() + b0, static_cast<hipStream_t>(stream));
-        }
-        return set_err(err, RS_OK);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored});
+            g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+            g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+            g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
+            if ((g.orig_bstride | g.rec_bstride | g.out_bstride) % 4) force_bytes(g, S);
+            for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
+                g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
+                decode_masks_dev(ctx, ws, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
+                                 orig_present + b0 * N, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride,
+                                 rec_present + b0 * M, static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
+                                 skip.data() + b0, s);
+            }
+        });
     });
 }
 
@@ -3467,10 +3471,7 @@ rs_status rs_repair_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
         std::vector<uint8_t> skip(stripes, 0);
         bool work = false;
         for (uint64_t b = 0; b < stripes; ++b) {
-            const uint8_t *op = orig_present + b * N, *rp = rec_present + b * M;
-            uint64_t have_o = 0, have_r = 0;
-            for (uint64_t i = 0; i < N; ++i) have_o += op[i] != 0;
-            for (uint64_t i = 0; i < M; ++i) have_r += rp[i] != 0;
+            const uint64_t have_o = count_selected(orig_present + b * N, N), have_r = count_selected(rec_present + b * M, M);
             if (stripe_status) stripe_status[b] = RS_OK;
             if (have_o + have_r < N) {
                 if (stripe_status) {
@@ -3478,39 +3479,30 @@ rs_status rs_repair_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
                     skip[b] = 2;
                     continue;
                 }
-                set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-                if (err) {
-                    err->original_count = N, err->original_received_count = have_o;
-                    err->recovery_received_count = have_r;
-                    err->index = b;  // the stripe, as rs_decode_device_batch_masks
-                }
+                not_enough_shards(err, N, have_o, have_r);
+                if (err) err->index = b;  // the stripe, as rs_decode_device_batch_masks
                 return RS_ERR_NOT_ENOUGH_SHARDS;
             }
             if (have_o == N && have_r == M) skip[b] = 1;
             else work = true;
         }
         if (!work) return set_err(err, RS_OK);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored, d_recovery_out},
-                             recovery_out_stride);
-        g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
-        g.out2_bstride = recovery_out_stripe_stride ? recovery_out_stripe_stride : M * g.out2();
-        if ((g.orig_bstride | g.rec_bstride | g.out_bstride | g.out2_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        StreamWs sw(ctx, static_cast<hipStream_t>(stream));
-        for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
-            g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
-            repair_masks_dev(ctx, sw.w, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
-                             orig_present + b0 * N, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride,
-                             rec_present + b0 * M, static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
-                             static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride, skip.data() + b0,
-                             static_cast<hipStream_t>(stream));
-        }
-        return set_err(err, RS_OK);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            Geom g = device_geom(S, orig_stride, rec_stride, restored_stride,
+                                 {d_orig, d_rec, d_restored, d_recovery_out}, recovery_out_stride);
+            g.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
+            g.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
+            g.out_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
+            g.out2_bstride = recovery_out_stripe_stride ? recovery_out_stripe_stride : M * g.out2();
+            if ((g.orig_bstride | g.rec_bstride | g.out_bstride | g.out2_bstride) % 4) force_bytes(g, S);
+            for (uint64_t b0 = 0; b0 < stripes; b0 += kMaxBatchStripes) {  // grid.y limit
+                g.stripes = uint32_t(std::min<uint64_t>(kMaxBatchStripes, stripes - b0));
+                repair_masks_dev(ctx, ws, high, g, N, M, static_cast<const uint8_t *>(d_orig) + b0 * g.orig_bstride,
+                                 orig_present + b0 * N, static_cast<const uint8_t *>(d_rec) + b0 * g.rec_bstride,
+                                 rec_present + b0 * M, static_cast<uint8_t *>(d_restored) + b0 * g.out_bstride,
+                                 static_cast<uint8_t *>(d_recovery_out) + b0 * g.out2_bstride, skip.data() + b0, s);
+            }
+        });
     });
 }
 
@@ -3549,10 +3541,7 @@ rs_status rs_update_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
     bool any = recovery_update == nullptr;
     for (uint64_t j = 0; !any && j < M; ++j) any = recovery_update[j] != 0;
     if (count == 0 || stripes == 0 || !any) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
+    return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
         Geom g = device_geom(S, d_old ? old_stride : 0, new_stride, recovery_stride, {d_old, d_new, d_recovery});
         UpdateCall U{N, M, S, count, stripes, index, static_cast<const uint8_t *>(d_old),
                      static_cast<const uint8_t *>(d_new), static_cast<uint8_t *>(d_recovery),
@@ -3560,12 +3549,8 @@ rs_status rs_update_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
         U.old_bstride = old_stripe_stride ? old_stripe_stride : count * U.old_stride;
         U.new_bstride = new_stripe_stride ? new_stripe_stride : count * U.new_stride;
         U.rec_bstride = recovery_stripe_stride ? recovery_stripe_stride : M * U.rec_stride;
-        if (stripes > 1 && ((d_old ? U.old_bstride : 0) | U.new_bstride | U.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        update_dev(ctx, sw.w, high != 0, g, U, s);
-        return set_err(err, RS_OK);
+        if (stripes > 1 && ((d_old ? U.old_bstride : 0) | U.new_bstride | U.rec_bstride) % 4) force_bytes(g, S);
+        update_dev(ctx, ws, high != 0, g, U, s);
     });
 }
 
@@ -3605,22 +3590,10 @@ rs_status rs_verify_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
             return set_err(err, RS_OK);
         });
     }
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                     0, 0, recovery_check, d_mismatch};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        verify_dev(ctx, sw.w, high != 0, g, V, s);
-        return set_err(err, RS_OK);
-    });
+    const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+    const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch);
+    return device_call(ctx, stream, err,
+                       [&](Workspace &ws, hipStream_t s) { verify_dev(ctx, ws, high != 0, c.g, c.V, s); });
 }
 
 rs_status rs_verify_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const void *d_orig,
@@ -3656,24 +3629,16 @@ rs_status rs_verify_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
             check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
             return set_err(err, RS_OK);
         }
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                     0, 0, recovery_check, d_mismatch};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        StreamWs sw(ctx, s);
-        // every flag is defined after the call: zero, then the kernels store the ones
-        check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
-        uint32_t L = 0;
-        const bool column = verify_column(ctx, high != 0, g, N, M, &L);
-        if (column && ctx->verify_masks_fused) verify_masks_fused(ctx, sw.w, high != 0, g, V, sel, L, s);
-        else masks_unfused(ctx, sw.w, high != 0, g, V, sel, column, nullptr, nullptr, s);
-        return set_err(err, RS_OK);
+        const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+        const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            // every flag is defined after the call: zero, then the kernels store the ones
+            check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
+            uint32_t L = 0;
+            const bool column = verify_column(ctx, high != 0, c.g, N, M, &L);
+            if (column && ctx->verify_masks_fused) verify_masks_fused(ctx, ws, high != 0, c.g, c.V, sel, L, s);
+            else masks_unfused(ctx, ws, high != 0, c.g, c.V, sel, column, nullptr, nullptr, s);
+        });
     });
 }
 
@@ -3696,31 +3661,14 @@ rs_status rs_locate_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint
     const int high = resolve(rate, N, M, S, err);
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t nsel = M;  // a ratio needs two rows; fewer: rs_verify_device
-    if (recovery_check) {
-        nsel = 0;
-        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
-    }
-    if (nsel < 2) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    // a ratio needs two rows; fewer: rs_verify_device
+    if (count_selected(recovery_check, M) < 2) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                      0, 0, recovery_check, d_mismatch},
-                     d_located};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        locate_dev(ctx, sw.w, high != 0, g, V, s);
-        return set_err(err, RS_OK);
-    });
+    const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+    const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch, d_located);
+    return device_call(ctx, stream, err,
+                       [&](Workspace &ws, hipStream_t s) { locate_dev(ctx, ws, high != 0, c.g, c.V, s); });
 }
 
 rs_status rs_locate_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const void *d_orig,
@@ -3742,40 +3690,19 @@ rs_status rs_locate_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
-    if (M < 2 || N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS)
-        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (M < 2 || !locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     return guarded(err, [&]() -> rs_status {
-        // every stripe's mask, in stripe order, before any device work: a ratio needs two rows
-        std::vector<StripeSel> sel(stripes);
-        for (uint64_t b = 0; b < stripes; ++b) {
-            sel[b] = stripe_sel(recovery_check + b * M, uint32_t(M));
-            if (stripe_status) stripe_status[b] = sel[b].nsel < 2 ? RS_ERR_INVALID_ARGUMENT : RS_OK;
-            if (sel[b].nsel >= 2) continue;
-            if (!stripe_status) {
-                set_err(err, RS_ERR_INVALID_ARGUMENT);
-                if (err) err->index = b;
-                return RS_ERR_INVALID_ARGUMENT;
-            }
-            sel[b] = StripeSel{uint32_t(M), 0, 0};  // skipped: none of its rows is read
-        }
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                     0, 0, recovery_check, d_mismatch};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        const uint16_t *logs = locate_table(ctx, sw.w, high != 0, N, M, s);
-        check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
-        uint32_t L = 0;
-        const bool column = verify_column(ctx, high != 0, g, N, M, &L);
-        masks_unfused(ctx, sw.w, high != 0, g, V, sel, column, d_located, logs, s);
-        return set_err(err, RS_OK);
+        std::vector<StripeSel> sel;  // a ratio needs two rows
+        if (!scan_stripe_masks(recovery_check, M, stripes, 2, stripe_status, sel, err)) return RS_ERR_INVALID_ARGUMENT;
+        const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+        const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            const uint16_t *logs = locate_table(ctx, ws, high != 0, N, M, s);
+            check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
+            uint32_t L = 0;
+            const bool column = verify_column(ctx, high != 0, c.g, N, M, &L);
+            masks_unfused(ctx, ws, high != 0, c.g, c.V, sel, column, d_located, logs, s);
+        });
     });
 }
 
@@ -3792,35 +3719,18 @@ rs_status rs_locate_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t 
     const int high = resolve(rate, N, M, S, err);
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t nsel = M;
-    if (recovery_check) {
-        nsel = 0;
-        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
-    }
+    const uint64_t nsel = count_selected(recovery_check, M);
     if (nsel < 2) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     // one clean pair among the first max_outliers + 1, and two clean rows shared by any two explanations
     if (max_outliers > RS_LOCATE_MAX_OUTLIERS || 2 * (1 + uint64_t(max_outliers)) > nsel)
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                      0, 0, recovery_check, d_mismatch},
-                     d_located};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        const RobustCall R{max_outliers, d_outlier};
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        locate_robust_dev(ctx, sw.w, high != 0, g, V, R, s);
-        return set_err(err, RS_OK);
-    });
+    const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+    const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch, d_located);
+    const RobustCall R{max_outliers, d_outlier};
+    return device_call(ctx, stream, err,
+                       [&](Workspace &ws, hipStream_t s) { locate_robust_dev(ctx, ws, high != 0, c.g, c.V, R, s); });
 }
 
 rs_status rs_locate_device_robust(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, const void *d_orig,
@@ -3846,21 +3756,12 @@ rs_status rs_locate_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || (d_restored && !stride_ok(restored_stride, S)))
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t have_o = 0, nsel = M;
-    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
-    if (recovery_check) {
-        nsel = 0;
-        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
-    }
+    const uint64_t have_o = count_selected(orig_present, N), nsel = count_selected(recovery_check, M);
     const uint64_t missing = N - have_o;
-    if (nsel < missing) {  // not decodable: the decode's error and counts
-        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = nsel;
-        return RS_ERR_NOT_ENOUGH_SHARDS;
-    }
+    if (nsel < missing) return not_enough_shards(err, N, have_o, nsel);  // not decodable: the decode's error and counts
     // decodable, but a ratio needs two rows beyond the reference rows
     if (nsel < missing + 2) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
     // nothing missing: the locate itself (its table, its launches; d_restored untouched)
     if (!missing)
@@ -3868,31 +3769,14 @@ rs_status rs_locate_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_
                                       rec_stride, rec_stripe_stride, recovery_check, d_located, d_mismatch, stream,
                                       err);
     return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        // (scratch rows are whole 64-byte blocks: neither stride of it forces the byte-wise path)
-        const uint64_t W = round_up(S, 64);
-        Geom g = d_restored ? device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored}, W)
-                            : device_geom(S, orig_stride, rec_stride, W, {d_orig, d_rec}, W);
-        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                      0, 0, recovery_check, d_mismatch},
-                     d_located};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        DegradedCall C;
-        C.present = orig_present;
-        C.d_restored = static_cast<uint8_t *>(d_restored);
-        C.restored_bstride = d_restored ? (restored_stripe_stride ? restored_stripe_stride : N * g.out()) : 0;
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride | C.restored_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        for (uint64_t j = 0; j < M; ++j)  // the selected rows in order: the first `missing` are R, the rest K
-            if (!recovery_check || recovery_check[j])
-                (C.ref.size() < missing ? C.ref : C.check).push_back(uint32_t(j));
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        locate_degraded_dev(ctx, sw.w, high != 0, g, V, C, s);
-        return set_err(err, RS_OK);
+        const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+        const Matrix restored{d_restored, restored_stride, restored_stripe_stride};
+        const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch, d_located, &restored);
+        DegradedCall C{orig_present, {}, {}, static_cast<uint8_t *>(d_restored), c.restored_bstride};
+        split_rows(recovery_check, M, missing, C);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            locate_degraded_dev(ctx, ws, high != 0, c.g, c.V, C, s);
+        });
     });
 }
 
@@ -3923,23 +3807,14 @@ rs_status rs_heal_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_t 
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S) || !stride_ok(restored_stride, S))
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t have_o = 0, nsel = M;
-    for (uint64_t i = 0; i < N; ++i) have_o += orig_present[i] != 0;
-    if (recovery_check) {
-        nsel = 0;
-        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
-    }
+    if (!heal_mode_ok(mode)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const uint64_t have_o = count_selected(orig_present, N), nsel = count_selected(recovery_check, M);
     const uint64_t missing = N - have_o;
-    if (nsel < missing) {  // not decodable: the decode's error and counts
-        set_err(err, RS_ERR_NOT_ENOUGH_SHARDS);
-        if (err) err->original_count = N, err->original_received_count = have_o, err->recovery_received_count = nsel;
-        return RS_ERR_NOT_ENOUGH_SHARDS;
-    }
+    if (nsel < missing) return not_enough_shards(err, N, have_o, nsel);  // not decodable: the decode's error and counts
     // three check rows to write on the evidence of a location (with two, two corrupt
     // information shards can be attributed to a third)
     if (nsel < missing + 3) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
     // nothing missing: the heal itself (its table, its launches; d_restored untouched)
     if (!missing)
@@ -3947,31 +3822,15 @@ rs_status rs_heal_device_degraded_batch(rs_context *ctx, rs_rate rate, uint64_t 
                                     rec_stride, rec_stripe_stride, recovery_check, mode, max_rows, d_located,
                                     d_mismatch, d_action, stream, err);
     return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        // (as rs_locate_device_degraded_batch, d_restored given)
-        const uint64_t W = round_up(S, 64);
-        Geom g = device_geom(S, orig_stride, rec_stride, restored_stride, {d_orig, d_rec, d_restored}, W);
-        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                      0, 0, recovery_check, d_mismatch},
-                     d_located};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        DegradedCall C;
-        C.present = orig_present;
-        C.d_restored = static_cast<uint8_t *>(d_restored);
-        C.restored_bstride = restored_stripe_stride ? restored_stripe_stride : N * g.out();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride | C.restored_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        for (uint64_t j = 0; j < M; ++j)  // the selected rows in order: the first `missing` are R, the rest K
-            if (!recovery_check || recovery_check[j])
-                (C.ref.size() < missing ? C.ref : C.check).push_back(uint32_t(j));
+        const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+        const Matrix restored{d_restored, restored_stride, restored_stripe_stride};
+        const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch, d_located, &restored);
+        DegradedCall C{orig_present, {}, {}, static_cast<uint8_t *>(d_restored), c.restored_bstride};
+        split_rows(recovery_check, M, missing, C);
         const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        locate_degraded_dev(ctx, sw.w, high != 0, g, V, C, s, &H);
-        return set_err(err, RS_OK);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            locate_degraded_dev(ctx, ws, high != 0, c.g, c.V, C, s, &H);
+        });
     });
 }
 
@@ -3997,35 +3856,18 @@ rs_status rs_heal_device_batch(rs_context *ctx, rs_rate rate, uint64_t N, uint64
     const int high = resolve(rate, N, M, S, err);
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t nsel = M;
-    if (recovery_check) {
-        nsel = 0;
-        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
-    }
+    if (!heal_mode_ok(mode)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     // the locate's two rows; three to write an original on the evidence (with two, two
     // corrupt originals can be attributed to a third)
-    if (nsel < ((mode & RS_HEAL_ORIGINAL) ? 3u : 2u)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (count_selected(recovery_check, M) < ((mode & RS_HEAL_ORIGINAL) ? 3u : 2u))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                      0, 0, recovery_check, d_mismatch},
-                     d_located};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        locate_dev(ctx, sw.w, high != 0, g, V, s, &H);
-        return set_err(err, RS_OK);
-    });
+    const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+    const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch, d_located);
+    const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
+    return device_call(ctx, stream, err,
+                       [&](Workspace &ws, hipStream_t s) { locate_dev(ctx, ws, high != 0, c.g, c.V, s, &H); });
 }
 
 rs_status rs_heal_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S, void *d_orig,
@@ -4048,52 +3890,31 @@ rs_status rs_heal_device_batch_masks(rs_context *ctx, rs_rate rate, uint64_t N, 
     const int high = resolve(rate, N, M, S, err);
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!heal_mode_ok(mode)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
     // the heal's own rule (rs_heal_device_batch), stripe by stripe
     const uint32_t need = (mode & RS_HEAL_ORIGINAL) ? 3u : 2u;
-    if (M < need || N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS)
-        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (M < need || !locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     return guarded(err, [&]() -> rs_status {
-        // every stripe's mask, in stripe order, before any device work
-        std::vector<StripeSel> sel(stripes);
-        for (uint64_t b = 0; b < stripes; ++b) {
-            sel[b] = stripe_sel(recovery_check + b * M, uint32_t(M));
-            if (stripe_status) stripe_status[b] = sel[b].nsel < need ? RS_ERR_INVALID_ARGUMENT : RS_OK;
-            if (sel[b].nsel >= need) continue;
-            if (!stripe_status) {
-                set_err(err, RS_ERR_INVALID_ARGUMENT);
-                if (err) err->index = b;
-                return RS_ERR_INVALID_ARGUMENT;
-            }
-            sel[b] = StripeSel{uint32_t(M), 0, 0};  // skipped: none of its rows is read or written
-        }
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        VerifyCall V{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                     0, 0, recovery_check, d_mismatch};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
+        std::vector<StripeSel> sel;
+        if (!scan_stripe_masks(recovery_check, M, stripes, need, stripe_status, sel, err)) return RS_ERR_INVALID_ARGUMENT;
+        const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+        const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch);
         const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        const uint16_t *logs = locate_table(ctx, sw.w, high != 0, N, M, s);
-        check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
-        uint32_t L = 0;
-        const bool column = verify_column(ctx, high != 0, g, N, M, &L);
-        // a group whose stripes are all skipped launches no k_heal_masks: their action is this
-        // zero.  (Every other group's launch stores all of its action bytes: a batch without
-        // such a group pays for no memset.)
-        bool idle = false;
-        for (uint64_t b0 = 0, group = column ? kMaxBatchStripes : 1; b0 < stripes && !idle; b0 += group)
-            idle = !union_sel(sel, b0, std::min<uint64_t>(b0 + group, stripes), uint32_t(M)).nsel;
-        if (idle) check(hipMemsetAsync(d_action, 0, stripes, s));
-        masks_unfused(ctx, sw.w, high != 0, g, V, sel, column, d_located, logs, s, &H);
-        return set_err(err, RS_OK);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            const uint16_t *logs = locate_table(ctx, ws, high != 0, N, M, s);
+            check(hipMemsetAsync(d_mismatch, 0, stripes * M, s));
+            uint32_t L = 0;
+            const bool column = verify_column(ctx, high != 0, c.g, N, M, &L);
+            // a group whose stripes are all skipped launches no k_heal_masks: their action is this
+            // zero.  (Every other group's launch stores all of its action bytes: a batch without
+            // such a group pays for no memset.)
+            bool idle = false;
+            for (uint64_t b0 = 0, group = column ? kMaxBatchStripes : 1; b0 < stripes && !idle; b0 += group)
+                idle = !union_sel(sel, b0, std::min<uint64_t>(b0 + group, stripes), uint32_t(M)).nsel;
+            if (idle) check(hipMemsetAsync(d_action, 0, stripes, s));
+            masks_unfused(ctx, ws, high != 0, c.g, c.V, sel, column, d_located, logs, s, &H);
+        });
     });
 }
 
@@ -4112,36 +3933,20 @@ rs_status rs_heal_device_robust_batch(rs_context *ctx, rs_rate rate, uint64_t N,
     const int high = resolve(rate, N, M, S, err);
     if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
     if (!stride_ok(orig_stride, S) || !stride_ok(rec_stride, S)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (!mode || (mode & ~(RS_HEAL_ORIGINAL | RS_HEAL_RECOVERY))) return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    uint64_t nsel = M;
-    if (recovery_check) {
-        nsel = 0;
-        for (uint64_t j = 0; j < M; ++j) nsel += recovery_check[j] != 0;
-    }
+    if (!heal_mode_ok(mode)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const uint64_t nsel = count_selected(recovery_check, M);
     // the heal's rows (three to write an original on the evidence), then the robust locate's
     if (nsel < ((mode & RS_HEAL_ORIGINAL) ? 3u : 2u)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (max_outliers > RS_LOCATE_MAX_OUTLIERS || 2 * (1 + uint64_t(max_outliers)) > nsel)
         return set_err(err, RS_ERR_INVALID_ARGUMENT);
-    if (N > RS_LOCATE_MAX_ORIGINALS || N * M > RS_LOCATE_MAX_COEFFICIENTS) return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (!locate_shape_ok(N, M)) return set_err(err, RS_ERR_INVALID_ARGUMENT);
     if (stripes == 0) return set_err(err, RS_OK);
-    return guarded(err, [&]() -> rs_status {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        ProfScope prof(ctx);
-        Geom g = device_geom(S, orig_stride, rec_stride, 0, {d_orig, d_rec});
-        LocateCall V{{N, M, S, stripes, static_cast<const uint8_t *>(d_orig), static_cast<const uint8_t *>(d_rec),
-                      0, 0, recovery_check, d_mismatch},
-                     d_located};
-        V.orig_bstride = orig_stripe_stride ? orig_stripe_stride : N * g.orig();
-        V.rec_bstride = rec_stripe_stride ? rec_stripe_stride : M * g.rec();
-        if (stripes > 1 && (V.orig_bstride | V.rec_bstride) % 4)
-            g.fmt.io_bytes = 1, g.fmt.full_packs = uint32_t(S / 64 * 8), g.fmt.tail_h = uint32_t(S % 64 / 2);
-        const RobustCall R{max_outliers, d_outlier};
-        const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
-        auto s = static_cast<hipStream_t>(stream);
-        StreamWs sw(ctx, s);
-        locate_robust_dev(ctx, sw.w, high != 0, g, V, R, s, &H);
-        return set_err(err, RS_OK);
+    const Matrix orig{d_orig, orig_stride, orig_stripe_stride}, rec{d_rec, rec_stride, rec_stripe_stride};
+    const ScrubCall c = scrub_call(N, M, S, stripes, orig, rec, recovery_check, d_mismatch, d_located);
+    const RobustCall R{max_outliers, d_outlier};
+    const HealCall H{static_cast<uint8_t *>(d_orig), static_cast<uint8_t *>(d_rec), mode, max_rows, d_action};
+    return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+        locate_robust_dev(ctx, ws, high != 0, c.g, c.V, R, s, &H);
     });
 }
 

@@ -824,21 +824,29 @@ def _batch_strides(x):
     return int(x.stride(1)) * x.element_size(), int(x.stride(0)) * x.element_size()
 
 
+def _batch_pair(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery) -> int:
+    """The two matrices of a *_batch call, [stripes, rows, shard_bytes] each: their stripe count.
+    (Their strides, _batch_strides, come after the call's other checks: the library's order.)"""
+    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    n = d_original.shape[0]
+    if d_recovery.shape[0] != n:
+        raise ValueError("original and recovery batches differ in stripe count")
+    return n
+
+
 def encode_device_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
                         stream=None, rate_: int = RATE_DEFAULT, ctx: Optional[Context] = None) -> None:
     """Encode a batch of stripes of one shape (rs_encode_device_batch): d_original
     [stripes, original_count, shard_bytes], d_recovery [stripes, recovery_count, shard_bytes]."""
     ctx = ctx or default_context()
     _validate(rate_, original_count, recovery_count, shard_bytes)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    if d_original.shape[0] != d_recovery.shape[0]:
-        raise ValueError("original and recovery batches differ in stripe count")
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
-    _raise(_lib.rs_encode_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
-                                       d_original.shape[0], d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(),
-                                       r_row, r_b, _stream(stream), ctypes.byref(err)), err)
+    _raise(_lib.rs_encode_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
+                                       d_original.data_ptr(), o_row, o_b, d_recovery.data_ptr(), r_row, r_b,
+                                       _stream(stream), ctypes.byref(err)), err)
 
 
 def decode_device_batch(original_count: int, recovery_count: int, shard_bytes: int, d_original, original_present,
@@ -1115,23 +1123,24 @@ VERIFY_FUSED_DEFAULT = 1  # RS_VERIFY_FUSED_DEFAULT (include/rs_mi355x.h)
 VERIFY_MASKS_FUSED_DEFAULT = 0  # RS_VERIFY_MASKS_FUSED_DEFAULT: verify_device_batch_masks' own default route
 
 
-def _check_flags(d_mismatch, shape, like):
-    """The flag tensor of a verify: the caller's (uint8, on the device, contiguous, exactly `shape`:
-    the library writes shape-product bytes, densely) or a new one on the device of `like`."""
-    if d_mismatch is None:
+def _check_output(x, name: str, dtype: str, shape, like):
+    """An output tensor of a verify, locate or heal (d_mismatch, d_located, d_outlier, d_action):
+    the caller's (of torch dtype `dtype`, on the device, contiguous, exactly `shape`: the library
+    writes shape-product elements, densely) or a new one on the device of `like`."""
+    if x is None:
         if not hasattr(like, "data_ptr"):
-            raise ValueError("d_mismatch: needed when the matrices are raw pointers")
+            raise ValueError(f"{name}: needed when the matrices are raw pointers")
         import torch
-        return torch.empty(shape, dtype=torch.uint8, device=like.device)
-    if hasattr(d_mismatch, "data_ptr"):
-        if str(d_mismatch.dtype) != "torch.uint8":
-            raise ValueError(f"d_mismatch: dtype must be uint8, got {d_mismatch.dtype}")
-        if not d_mismatch.is_cuda:
-            raise ValueError("d_mismatch: must be a device (cuda/HIP) tensor")
-        if tuple(d_mismatch.shape) != tuple(shape) or not d_mismatch.is_contiguous():
-            raise ValueError(f"d_mismatch: expected a contiguous tensor of shape {tuple(shape)}, "
-                             f"got {tuple(d_mismatch.shape)}")
-    return d_mismatch
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=like.device)
+    if hasattr(x, "data_ptr"):
+        if str(x.dtype) != f"torch.{dtype}":
+            raise ValueError(f"{name}: dtype must be {dtype}, got {x.dtype}")
+        if not x.is_cuda:
+            raise ValueError(f"{name}: must be a device (cuda/HIP) tensor")
+        if tuple(x.shape) != tuple(shape) or not x.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous tensor of shape {tuple(shape)}, "
+                             f"got {tuple(x.shape)}")
+    return x
 
 
 def verify_device(original_count: int, recovery_count: int, shard_bytes: int, d_original, d_recovery,
@@ -1148,7 +1157,7 @@ def verify_device(original_count: int, recovery_count: int, shard_bytes: int, d_
                                                           "recovery_rows")
     _check_matrix(d_original, original_count, shard_bytes, "d_original")
     _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
-    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (recovery_count,), d_recovery)
     err = _RsError()
     _raise(_lib.rs_verify_device(ctx.handle, rate_, original_count, recovery_count, shard_bytes, _ptr(d_original),
                                  _row_stride(d_original), _ptr(d_recovery), _row_stride(d_recovery), rows,
@@ -1165,12 +1174,8 @@ def verify_device_batch(original_count: int, recovery_count: int, shard_bytes: i
     _validate(rate_, original_count, recovery_count, shard_bytes)
     rows = None if recovery_rows is None else _check_mask(present_mask(recovery_rows), recovery_count,
                                                           "recovery_rows")
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_verify_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
@@ -1188,13 +1193,9 @@ def verify_device_batch_masks(original_count: int, recovery_count: int, shard_by
     leaves out are never read in that stripe.  Returns the flag tensor [stripes, recovery_count]."""
     ctx = ctx or default_context()
     _validate(rate_, original_count, recovery_count, shard_bytes)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
     rows = _stripe_masks(recovery_rows, n, recovery_count, "recovery_rows")
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_verify_device_batch_masks(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
@@ -1216,25 +1217,6 @@ LOCATE_CLEAN = -1    # RS_LOCATE_CLEAN (include/rs_mi355x.h)
 LOCATE_ROWS = -2     # RS_LOCATE_ROWS
 LOCATE_UNKNOWN = -3  # RS_LOCATE_UNKNOWN
 LOCATE_SKIPPED = -4  # RS_LOCATE_SKIPPED (locate_device_batch_masks, status=True)
-
-
-def _check_located(d_located, shape, like):
-    """The result tensor of a locate: the caller's (int32, on the device, contiguous, exactly
-    `shape`) or a new one on the device of `like`."""
-    if d_located is None:
-        if not hasattr(like, "data_ptr"):
-            raise ValueError("d_located: needed when the matrices are raw pointers")
-        import torch
-        return torch.empty(shape, dtype=torch.int32, device=like.device)
-    if hasattr(d_located, "data_ptr"):
-        if str(d_located.dtype) != "torch.int32":
-            raise ValueError(f"d_located: dtype must be int32, got {d_located.dtype}")
-        if not d_located.is_cuda:
-            raise ValueError("d_located: must be a device (cuda/HIP) tensor")
-        if tuple(d_located.shape) != tuple(shape) or not d_located.is_contiguous():
-            raise ValueError(f"d_located: expected a contiguous tensor of shape {tuple(shape)}, "
-                             f"got {tuple(d_located.shape)}")
-    return d_located
 
 
 def _locate_mask(recovery_rows, recovery_count):
@@ -1259,8 +1241,8 @@ def locate_device(original_count: int, recovery_count: int, shard_bytes: int, d_
     rows = _locate_mask(recovery_rows, recovery_count)
     _check_matrix(d_original, original_count, shard_bytes, "d_original")
     _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
-    d_located = _check_located(d_located, (1,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (1,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (recovery_count,), d_recovery)
     err = _RsError()
     _raise(_lib.rs_locate_device(ctx.handle, rate_, original_count, recovery_count, shard_bytes, _ptr(d_original),
                                  _row_stride(d_original), _ptr(d_recovery), _row_stride(d_recovery), rows,
@@ -1276,13 +1258,9 @@ def locate_device_batch(original_count: int, recovery_count: int, shard_bytes: i
     ctx = ctx or default_context()
     _validate(rate_, original_count, recovery_count, shard_bytes)
     rows = _locate_mask(recovery_rows, recovery_count)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_locate_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
@@ -1307,14 +1285,10 @@ def locate_device_batch_masks(original_count: int, recovery_count: int, shard_by
     _validate(rate_, original_count, recovery_count, shard_bytes)
     if recovery_count < 2:
         raise ValueError("recovery_rows: a locate needs two recovery rows at least (verify_device takes fewer)")
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
     rows = _stripe_masks(recovery_rows, n, recovery_count, "recovery_rows")
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     codes = (ctypes.c_uint8 * n)() if status else None
     err = _RsError()
@@ -1336,25 +1310,6 @@ def locate_device_batch_masks(original_count: int, recovery_count: int, shard_by
 
 
 LOCATE_MAX_OUTLIERS = 7  # RS_LOCATE_MAX_OUTLIERS (include/rs_mi355x.h)
-
-
-def _check_outlier(d_outlier, shape, like):
-    """The outlier tensor of a robust locate: the caller's (uint8, on the device, contiguous,
-    exactly `shape`) or a new one on the device of `like`."""
-    if d_outlier is None:
-        if not hasattr(like, "data_ptr"):
-            raise ValueError("d_outlier: needed when the matrices are raw pointers")
-        import torch
-        return torch.empty(shape, dtype=torch.uint8, device=like.device)
-    if hasattr(d_outlier, "data_ptr"):
-        if str(d_outlier.dtype) != "torch.uint8":
-            raise ValueError(f"d_outlier: dtype must be uint8, got {d_outlier.dtype}")
-        if not d_outlier.is_cuda:
-            raise ValueError("d_outlier: must be a device (cuda/HIP) tensor")
-        if tuple(d_outlier.shape) != tuple(shape) or not d_outlier.is_contiguous():
-            raise ValueError(f"d_outlier: expected a contiguous tensor of shape {tuple(shape)}, "
-                             f"got {tuple(d_outlier.shape)}")
-    return d_outlier
 
 
 def _robust_args(recovery_rows, recovery_count, max_outliers):
@@ -1382,9 +1337,9 @@ def locate_device_robust(original_count: int, recovery_count: int, shard_bytes: 
     rows, t = _robust_args(recovery_rows, recovery_count, max_outliers)
     _check_matrix(d_original, original_count, shard_bytes, "d_original")
     _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
-    d_located = _check_located(d_located, (1,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
-    d_outlier = _check_outlier(d_outlier, (recovery_count,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (1,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (recovery_count,), d_recovery)
+    d_outlier = _check_output(d_outlier, "d_outlier", "uint8", (recovery_count,), d_recovery)
     err = _RsError()
     _raise(_lib.rs_locate_device_robust(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
                                         _ptr(d_original), _row_stride(d_original), _ptr(d_recovery),
@@ -1403,14 +1358,10 @@ def locate_device_robust_batch(original_count: int, recovery_count: int, shard_b
     ctx = ctx or default_context()
     _validate(rate_, original_count, recovery_count, shard_bytes)
     rows, t = _robust_args(recovery_rows, recovery_count, max_outliers)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
-    d_outlier = _check_outlier(d_outlier, (n, recovery_count), d_recovery)
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
+    d_outlier = _check_output(d_outlier, "d_outlier", "uint8", (n, recovery_count), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_locate_device_robust_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
@@ -1453,8 +1404,8 @@ def locate_device_degraded(original_count: int, recovery_count: int, shard_bytes
     _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
     if d_restored is not None:
         _check_matrix(d_restored, original_count, shard_bytes, "d_restored")
-    d_located = _check_located(d_located, (1,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (1,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (recovery_count,), d_recovery)
     err = _RsError()
     _raise(_lib.rs_locate_device_degraded(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
                                           _ptr(d_original), _row_stride(d_original), present, _ptr(d_recovery),
@@ -1475,19 +1426,15 @@ def locate_device_degraded_batch(original_count: int, recovery_count: int, shard
     ctx = ctx or default_context()
     _validate(rate_, original_count, recovery_count, shard_bytes)
     present, rows = _degraded_masks(original_present, original_count, recovery_rows, recovery_count)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
     x_row = x_b = 0
     if d_restored is not None:
         _check_matrix(d_restored, original_count, shard_bytes, "d_restored", 3)
         if d_restored.shape[0] != n:
             raise ValueError("original and restored batches differ in stripe count")
         x_row, x_b = _batch_strides(d_restored)
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_locate_device_degraded_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
@@ -1501,25 +1448,6 @@ def locate_device_degraded_batch(original_count: int, recovery_count: int, shard
 
 HEAL_ORIGINAL = 1  # RS_HEAL_ORIGINAL (include/rs_mi355x.h)
 HEAL_RECOVERY = 2  # RS_HEAL_RECOVERY
-
-
-def _check_action(d_action, shape, like):
-    """The action tensor of a heal: the caller's (uint8, on the device, contiguous, exactly
-    `shape`) or a new one on the device of `like`."""
-    if d_action is None:
-        if not hasattr(like, "data_ptr"):
-            raise ValueError("d_action: needed when the matrices are raw pointers")
-        import torch
-        return torch.empty(shape, dtype=torch.uint8, device=like.device)
-    if hasattr(d_action, "data_ptr"):
-        if str(d_action.dtype) != "torch.uint8":
-            raise ValueError(f"d_action: dtype must be uint8, got {d_action.dtype}")
-        if not d_action.is_cuda:
-            raise ValueError("d_action: must be a device (cuda/HIP) tensor")
-        if tuple(d_action.shape) != tuple(shape) or not d_action.is_contiguous():
-            raise ValueError(f"d_action: expected a contiguous tensor of shape {tuple(shape)}, "
-                             f"got {tuple(d_action.shape)}")
-    return d_action
 
 
 def _heal_args(recovery_rows, recovery_count, mode, max_rows):
@@ -1550,9 +1478,9 @@ def heal_device(original_count: int, recovery_count: int, shard_bytes: int, d_or
     rows, mode, max_rows = _heal_args(recovery_rows, recovery_count, mode, max_rows)
     _check_matrix(d_original, original_count, shard_bytes, "d_original")
     _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
-    d_located = _check_located(d_located, (1,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
-    d_action = _check_action(d_action, (1,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (1,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (recovery_count,), d_recovery)
+    d_action = _check_output(d_action, "d_action", "uint8", (1,), d_recovery)
     err = _RsError()
     _raise(_lib.rs_heal_device(ctx.handle, rate_, original_count, recovery_count, shard_bytes, _ptr(d_original),
                                _row_stride(d_original), _ptr(d_recovery), _row_stride(d_recovery), rows, mode,
@@ -1571,14 +1499,10 @@ def heal_device_batch(original_count: int, recovery_count: int, shard_bytes: int
     ctx = ctx or default_context()
     _validate(rate_, original_count, recovery_count, shard_bytes)
     rows, mode, max_rows = _heal_args(recovery_rows, recovery_count, mode, max_rows)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
-    d_action = _check_action(d_action, (n,), d_recovery)
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
+    d_action = _check_output(d_action, "d_action", "uint8", (n,), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_heal_device_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
@@ -1613,15 +1537,11 @@ def heal_device_batch_masks(original_count: int, recovery_count: int, shard_byte
     need = 3 if mode & HEAL_ORIGINAL else 2
     if recovery_count < need:
         raise ValueError(f"recovery_rows: this heal needs {need} recovery rows at least (three with HEAL_ORIGINAL)")
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
     rows = _stripe_masks(recovery_rows, n, recovery_count, "recovery_rows")
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
-    d_action = _check_action(d_action, (n,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
+    d_action = _check_output(d_action, "d_action", "uint8", (n,), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     codes = (ctypes.c_uint8 * n)() if status else None
     err = _RsError()
@@ -1685,9 +1605,9 @@ def heal_device_degraded(original_count: int, recovery_count: int, shard_bytes: 
     if d_restored is None:
         raise ValueError("d_restored: a degraded heal needs it (it may be d_original)")
     _check_matrix(d_restored, original_count, shard_bytes, "d_restored")
-    d_located = _check_located(d_located, (1,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
-    d_action = _check_action(d_action, (1,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (1,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (recovery_count,), d_recovery)
+    d_action = _check_output(d_action, "d_action", "uint8", (1,), d_recovery)
     err = _RsError()
     _raise(_lib.rs_heal_device_degraded(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
                                         _ptr(d_original), _row_stride(d_original), present, _ptr(d_recovery),
@@ -1709,20 +1629,16 @@ def heal_device_degraded_batch(original_count: int, recovery_count: int, shard_b
     _validate(rate_, original_count, recovery_count, shard_bytes)
     present, rows, mode, max_rows = _heal_degraded_args(original_present, original_count, recovery_rows,
                                                         recovery_count, mode, max_rows)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
     if d_restored is None:
         raise ValueError("d_restored: a degraded heal needs it (it may be d_original)")
     _check_matrix(d_restored, original_count, shard_bytes, "d_restored", 3)
     if d_restored.shape[0] != n:
         raise ValueError("original and restored batches differ in stripe count")
     x_row, x_b = _batch_strides(d_restored)
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
-    d_action = _check_action(d_action, (n,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
+    d_action = _check_output(d_action, "d_action", "uint8", (n,), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_heal_device_degraded_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
@@ -1756,10 +1672,10 @@ def heal_device_robust(original_count: int, recovery_count: int, shard_bytes: in
     rows, t, mode, max_rows = _heal_robust_args(recovery_rows, recovery_count, max_outliers, mode, max_rows)
     _check_matrix(d_original, original_count, shard_bytes, "d_original")
     _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery")
-    d_located = _check_located(d_located, (1,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (recovery_count,), d_recovery)
-    d_outlier = _check_outlier(d_outlier, (recovery_count,), d_recovery)
-    d_action = _check_action(d_action, (1,), d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (1,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (recovery_count,), d_recovery)
+    d_outlier = _check_output(d_outlier, "d_outlier", "uint8", (recovery_count,), d_recovery)
+    d_action = _check_output(d_action, "d_action", "uint8", (1,), d_recovery)
     err = _RsError()
     _raise(_lib.rs_heal_device_robust(ctx.handle, rate_, original_count, recovery_count, shard_bytes,
                                       _ptr(d_original), _row_stride(d_original), _ptr(d_recovery),
@@ -1780,15 +1696,11 @@ def heal_device_robust_batch(original_count: int, recovery_count: int, shard_byt
     ctx = ctx or default_context()
     _validate(rate_, original_count, recovery_count, shard_bytes)
     rows, t, mode, max_rows = _heal_robust_args(recovery_rows, recovery_count, max_outliers, mode, max_rows)
-    _check_matrix(d_original, original_count, shard_bytes, "d_original", 3)
-    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
-    n = d_original.shape[0]
-    if d_recovery.shape[0] != n:
-        raise ValueError("original and recovery batches differ in stripe count")
-    d_located = _check_located(d_located, (n,), d_recovery)
-    d_mismatch = _check_flags(d_mismatch, (n, recovery_count), d_recovery)
-    d_outlier = _check_outlier(d_outlier, (n, recovery_count), d_recovery)
-    d_action = _check_action(d_action, (n,), d_recovery)
+    n = _batch_pair(original_count, recovery_count, shard_bytes, d_original, d_recovery)
+    d_located = _check_output(d_located, "d_located", "int32", (n,), d_recovery)
+    d_mismatch = _check_output(d_mismatch, "d_mismatch", "uint8", (n, recovery_count), d_recovery)
+    d_outlier = _check_output(d_outlier, "d_outlier", "uint8", (n, recovery_count), d_recovery)
+    d_action = _check_output(d_action, "d_action", "uint8", (n,), d_recovery)
     (o_row, o_b), (r_row, r_b) = _batch_strides(d_original), _batch_strides(d_recovery)
     err = _RsError()
     _raise(_lib.rs_heal_device_robust_batch(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n,
