@@ -34,8 +34,9 @@
  *   batch decode with an erasure pattern per stripe)
  *   rs_repair_device (+ _strided, + _batch; rs_repair_device_batch_masks: a
  *   pattern per stripe): the decode that also rebuilds missing recovery shards
- *   rs_update_device (+ _batch): a partial-stripe write applied to the recovery
- *   shards in place, from the changed originals' deltas alone
+ *   rs_update_device (+ _batch; rs_update_device_batch_lists: an index list per
+ *   stripe): a partial-stripe write applied to the recovery shards in place,
+ *   from the changed originals' deltas alone
  *   rs_verify_device (+ _batch): which recovery shards no longer agree with the
  *   originals
  *   rs_locate_device (+ _batch): the verify that also names the one corrupt
@@ -470,6 +471,78 @@ rs_status rs_update_device_batch(rs_context *ctx, rs_rate rate, uint64_t origina
                                  void *d_recovery, uint64_t recovery_stride, uint64_t recovery_stripe_stride,
                                  const uint8_t *recovery_update, void *stream, rs_error *err);
 rs_status rs_update_set_direct_max(rs_context *ctx, uint32_t k);
+
+/* ---- update, one index list per stripe ----
+ * A batch of partial-stripe writes: every stripe overwrites its OWN originals and
+ * takes its OWN recovery-row mask, as the _masks calls of the decode, the repair,
+ * the verify, the locate and the heal do.
+ *   index: HOST array of stripes x max_count original indices, stripe-major;
+ * count: HOST array of `stripes` values, each <= max_count.  Stripe b overwrites
+ * originals index[b * max_count + c], c < count[b]; row c of stripe b of d_old /
+ * d_new is the old / new content of that original (d_old == NULL: d_new holds the
+ * deltas).  Rows c >= count[b] of a stripe's d_old / d_new are never read.  Stripe
+ * strides of 0 mean max_count rows for d_old / d_new and recovery_count rows for
+ * d_recovery.
+ *   recovery_update: NULL (every row of every stripe) or a HOST array of stripes x
+ * recovery_count bytes of 0/1, stripe-major: one mask per stripe.  Rows a stripe's
+ * mask marks 0 are neither read nor written in that stripe.
+ *   Row strides, alignment, the byte-wise path, the block and tail layout, no
+ * overlap of d_old / d_new with d_recovery: as in the shared-list batch call above.
+ * Asynchronous on `stream`, scratch per (context, stream).  The lists, the counts
+ * and the masks may be reused or freed as soon as the call returns: they travel
+ * through the stream's pinned staging (which waits for the copy that last read it)
+ * and their device copy is reused in stream order.
+ *   Result: stripe b ends exactly as if rs_update_device had been called on it with
+ * its own list and its own mask row.  A stripe with count[b] == 0, or whose mask
+ * selects nothing, is neither read nor written.  The call is all or nothing; there
+ * is no status array.
+ *   Errors, all before any device work, in this order:
+ *   1. null context, d_new or d_recovery, null count with stripes > 0, null index
+ *      with stripes > 0 and max_count > 0 -> RS_ERR_INVALID_ARGUMENT;
+ *   2. rs_validate;
+ *   3. the row strides -> RS_ERR_INVALID_ARGUMENT;
+ *   4. stripes == 0 or max_count == 0: RS_OK;
+ *   5. every stripe's list, in stripe order, the first offender decides, and
+ *      err->got carries the stripe's number (an extension, like err->index of the
+ *      _masks calls): count[b] > max_count -> RS_ERR_INVALID_ARGUMENT; an index >=
+ *      original_count -> InvalidOriginalShardIndex (original_count, index); an index
+ *      repeated within the stripe -> DuplicateOriginalShardIndex (index).  The same
+ *      index in two stripes is fine;
+ *   6. every count 0, or no stripe with a list selects a row: RS_OK, nothing
+ *      launched, the context not touched.
+ *   Routes.  Where original_count <= RS_LOCATE_MAX_ORIGINALS and original_count x
+ * recovery_count <= RS_LOCATE_MAX_COEFFICIENTS, every stripe with count[b] <=
+ * min(direct_max, 256) goes into ONE launch of k_update_lists per 65535 stripes.  Its
+ * coefficients are the locate's table of log G[j][i] over every original, the same
+ * object: built by the stream's first locate OR first such update of a (rate,
+ * original_count, recovery_count) and kept as the locate keeps it, so no index list
+ * costs a coefficient step.  The per-list table of rs_update_device is not touched.
+ * max_count is only the pitch of `index` and the default stripe stride of d_old /
+ * d_new: the lists are staged at the pitch of the longest launched one.
+ * Every other stripe (count[b] > direct_max, a shape beyond the bound, every stripe
+ * with direct_max == 0) carries count 0 in that launch and then runs on its own,
+ * one stripe after another, by whatever route rs_update_device takes for its list
+ * and mask row: THAT path pays the coefficient step (or the re-encode) per stripe.
+ *   Measured (tools/update_lists_time.py, profiles/update_lists/update_lists_time.txt;
+ * 1024:1024, delta form, every recovery row, k random indices per stripe that differ
+ * between stripes, us per call; shared = the shared-list batch call with stripe 0's
+ * list, which computes something else; loop = one rs_update_device per stripe):
+ *     batch          k   this call warm   shared    loop   this call cold
+ *     64 x 1 KiB     1             51.5     35.0    1722              508
+ *     64 x 1 KiB     8            108.8     79.1    1905              600
+ *      1 x 64 KiB    1             54.0     34.7    33.2              510
+ *      1 x 64 KiB    8            133.0     80.9    78.3              601
+ * 17-33 times faster than the loop for the 64-stripe batch, but 38-64 % slower than
+ * the shared-list call where that is an option: k_update_lists takes 48-129 us where
+ * k_update takes 35-85 (its logs lie a table row apart).  For a single stripe use
+ * rs_update_device.  The whole account: DESIGN.md "Update", an index list per stripe. */
+rs_status rs_update_device_batch_lists(rs_context *ctx, rs_rate rate, uint64_t original_count,
+                                       uint64_t recovery_count, uint64_t shard_bytes, uint64_t stripes,
+                                       const uint64_t *index, const uint32_t *count, uint64_t max_count,
+                                       const void *d_old, uint64_t old_stride, uint64_t old_stripe_stride,
+                                       const void *d_new, uint64_t new_stride, uint64_t new_stripe_stride,
+                                       void *d_recovery, uint64_t recovery_stride, uint64_t recovery_stripe_stride,
+                                       const uint8_t *recovery_update, void *stream, rs_error *err);
 
 /* ---- verify: do the recovery shards still agree with the originals? ----
  * The first step of a scrub.  Silent corruption (a flipped bit on a disk or in a

@@ -160,6 +160,10 @@ struct PinnedBuf {
 struct UpdateWs {
     DevBuf unit, coef, logs, d_lists, delta, enc;
     PinnedBuf h_lists;
+    // rs_update_device_batch_lists: a group's counts, index lists and selection bytes,
+    // staged anew by every call
+    DevBuf d_stripes;
+    PinnedBuf h_stripes;
     std::vector<uint32_t> lists;  // what d_lists holds: the index list, then the selected rows
     bool lists_valid = false;
     bool coef_valid = false;  // `logs` holds the table of (coef_high, coef_n, coef_m, coef_index)
@@ -2138,6 +2142,86 @@ const uint16_t *locate_table(rs_context *ctx, Workspace &ws, bool high, uint64_t
     return logs;
 }
 
+// update_dev's sibling with a list and a mask row per stripe (rs_update_device_batch_lists;
+// here because its coefficients are locate_table's).  nsel[b]: the rows stripe b selects, 0
+// where its list is empty too -- such a stripe is left alone.  Stripes of at most
+// min(direct_max, kUpdateDirectCap) indices, in a shape within the table's bound, go into one
+// k_update_lists launch per kMaxBatchStripes stripes (grid.z limit): their counts, lists (at the
+// pitch of the group's longest launched list, whatever max_count is) and selection bytes travel through the stream's staging (UpdateWs::h_stripes -> d_stripes, as
+// verify_masks_fused stages its masks), every other stripe with count 0.  Those run afterwards
+// through update_dev, one stripe at a time, and pay its coefficient step each.
+struct UpdateListsCall {
+    uint64_t N, M, S, max_count, stripes;
+    const uint64_t *index;  // stripes x max_count
+    const uint32_t *count;  // stripes
+    const uint8_t *d_old, *d_new;
+    uint8_t *d_rec;
+    uint64_t old_stride, new_stride, rec_stride;     // row strides, bytes
+    uint64_t old_bstride, new_bstride, rec_bstride;  // stripe strides, bytes
+    const uint8_t *mask;                             // stripes x M, nullptr: every recovery row
+};
+
+void update_lists_dev(rs_context *ctx, Workspace &ws, bool high, const Geom &g, const UpdateListsCall &U,
+                      const std::vector<uint32_t> &nsel, hipStream_t s) {
+    const uint64_t M = U.M, K = U.max_count;
+    const bool in_bound = U.N <= RS_LOCATE_MAX_ORIGINALS && U.N * U.M <= RS_LOCATE_MAX_COEFFICIENTS;
+    const uint32_t cap = in_bound ? std::min(ctx->update_direct_max, kUpdateDirectCap) : 0;
+    auto launched = [&](uint64_t b) { return nsel[b] && U.count[b] <= cap; };
+    bool any = false;
+    for (uint64_t b = 0; !any && b < U.stripes; ++b) any = launched(b);
+    if (any) {
+        if (!ws.upd) ws.upd.reset(new UpdateWs);
+        UpdateWs &u = *ws.upd;
+        rs::UpdateListsArgs A;
+        A.old_stride = U.old_stride, A.new_stride = U.new_stride, A.rec_stride = U.rec_stride;
+        A.old_bstride = U.old_bstride, A.new_bstride = U.new_bstride, A.rec_bstride = U.rec_bstride;
+        A.packs = g.packs, A.N = uint32_t(U.N), A.M = uint32_t(M);
+        A.logs = locate_table(ctx, ws, high, U.N, U.M, s);
+        A.lut = ctx->d_lut;
+        A.fmt = g.fmt;
+        const uint64_t pack_bytes = uint64_t(g.packs) * 8;
+        for (uint64_t b0 = 0; b0 < U.stripes; b0 += kMaxBatchStripes) {
+            const uint64_t nb = std::min<uint64_t>(kMaxBatchStripes, U.stripes - b0);
+            uint64_t rows = 0;
+            uint32_t P = 0;  // the staged lists' pitch: the group's longest launched list (<= cap), not max_count
+            for (uint64_t b = b0; b < b0 + nb; ++b)
+                if (launched(b)) {
+                    rows += 2 * uint64_t(nsel[b]) + uint64_t(U.count[b]) * (U.d_old ? 2 : 1);
+                    P = std::max(P, U.count[b]);
+                }
+            if (!rows) continue;
+            const size_t index_off = nb * 4, sel_off = index_off + nb * size_t(P) * 4;
+            const size_t bytes = sel_off + (U.mask ? round_up(nb * M, 4) : 0);
+            uint8_t *h = u.h_stripes.get(bytes);
+            uint32_t *hc = reinterpret_cast<uint32_t *>(h), *hi = reinterpret_cast<uint32_t *>(h + index_off);
+            for (uint64_t b = 0; b < nb; ++b) {
+                hc[b] = launched(b0 + b) ? U.count[b0 + b] : 0;
+                for (uint64_t c = 0; c < P; ++c) hi[b * P + c] = c < hc[b] ? uint32_t(U.index[(b0 + b) * K + c]) : 0;
+                for (uint64_t j = 0; U.mask && j < M; ++j) h[sel_off + b * M + j] = U.mask[(b0 + b) * M + j] != 0;
+            }
+            uint8_t *d = static_cast<uint8_t *>(u.d_stripes.get(bytes));
+            check(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+            u.h_stripes.copied_on(s);
+            A.stripes = uint32_t(nb), A.index_pitch = P;
+            A.counts = reinterpret_cast<const uint32_t *>(d);
+            A.index = reinterpret_cast<const uint32_t *>(d + index_off);
+            A.sel = U.mask ? d + sel_off : nullptr;
+            A.old_rows = U.d_old ? U.d_old + b0 * U.old_bstride : nullptr;
+            A.new_rows = U.d_new + b0 * U.new_bstride;
+            A.rec = U.d_rec + b0 * U.rec_bstride;
+            update_launch(s, rows * pack_bytes, [&] { return rs::launch_update_lists(A, s); });
+        }
+    }
+    for (uint64_t b = 0; b < U.stripes; ++b) {
+        if (!nsel[b] || launched(b)) continue;
+        UpdateCall One{U.N, U.M, U.S, U.count[b], 1, U.index + b * K,
+                       U.d_old ? U.d_old + b * U.old_bstride : nullptr, U.d_new + b * U.new_bstride,
+                       U.d_rec + b * U.rec_bstride, U.old_stride, U.new_stride, U.rec_stride,
+                       U.old_bstride, U.new_bstride, U.rec_bstride, U.mask ? U.mask + b * M : nullptr};
+        update_dev(ctx, ws, high, g, One, s);
+    }
+}
+
 struct LocateCall : VerifyCall {
     int32_t *d_located;  // one per stripe
 };
@@ -3560,6 +3644,58 @@ rs_status rs_update_device(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M
                            const uint8_t *recovery_update, void *stream, rs_error *err) {
     return rs_update_device_batch(ctx, rate, N, M, S, 1, index, count, d_old, old_stride, 0, d_new, new_stride, 0,
                                   d_recovery, recovery_stride, 0, recovery_update, stream, err);
+}
+
+rs_status rs_update_device_batch_lists(rs_context *ctx, rs_rate rate, uint64_t N, uint64_t M, uint64_t S,
+                                       uint64_t stripes, const uint64_t *index, const uint32_t *count,
+                                       uint64_t max_count, const void *d_old, uint64_t old_stride,
+                                       uint64_t old_stripe_stride, const void *d_new, uint64_t new_stride,
+                                       uint64_t new_stripe_stride, void *d_recovery, uint64_t recovery_stride,
+                                       uint64_t recovery_stripe_stride, const uint8_t *recovery_update, void *stream,
+                                       rs_error *err) {
+    if (!ctx || !ptr_ok(d_new) || !ptr_ok(d_recovery) || (!count && stripes > 0) ||
+        (!index && stripes > 0 && max_count > 0))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    const int high = resolve(rate, N, M, S, err);
+    if (high < 0) return rs_status(err ? err->code : RS_ERR_UNSUPPORTED_SHARD_COUNT);
+    if ((d_old && !stride_ok(old_stride, S)) || !stride_ok(new_stride, S) || !stride_ok(recovery_stride, S))
+        return set_err(err, RS_ERR_INVALID_ARGUMENT);
+    if (stripes == 0 || max_count == 0) return set_err(err, RS_OK);
+    return guarded(err, [&]() -> rs_status {
+        // every stripe's list, in stripe order, before any device work; err->got: the stripe
+        std::vector<uint64_t> seen(N, 0);  // the last stripe (+ 1) that named the original
+        std::vector<uint32_t> nsel(stripes, 0);
+        bool any = false;
+        for (uint64_t b = 0; b < stripes; ++b) {
+            auto fail = [&](rs_status code, uint64_t original_count, uint64_t i) {
+                set_err(err, code);
+                if (err) err->original_count = original_count, err->index = i, err->got = b;
+                return code;
+            };
+            if (count[b] > max_count) return fail(RS_ERR_INVALID_ARGUMENT, 0, 0);
+            for (uint64_t c = 0; c < count[b]; ++c) {
+                const uint64_t i = index[b * max_count + c];
+                if (i >= N) return fail(RS_ERR_INVALID_ORIGINAL_SHARD_INDEX, N, i);
+                if (seen[i] == b + 1) return fail(RS_ERR_DUPLICATE_ORIGINAL_SHARD_INDEX, 0, i);
+                seen[i] = b + 1;
+            }
+            if (count[b]) nsel[b] = uint32_t(count_selected(recovery_update ? recovery_update + b * M : nullptr, M));
+            any = any || nsel[b];
+        }
+        // nothing to change: nothing launched, nothing written, the context not touched
+        if (!any) return set_err(err, RS_OK);
+        return device_call(ctx, stream, err, [&](Workspace &ws, hipStream_t s) {
+            Geom g = device_geom(S, d_old ? old_stride : 0, new_stride, recovery_stride, {d_old, d_new, d_recovery});
+            UpdateListsCall U{N, M, S, max_count, stripes, index, count, static_cast<const uint8_t *>(d_old),
+                              static_cast<const uint8_t *>(d_new), static_cast<uint8_t *>(d_recovery),
+                              g.orig(), g.rec(), g.out(), 0, 0, 0, recovery_update};
+            U.old_bstride = old_stripe_stride ? old_stripe_stride : max_count * U.old_stride;
+            U.new_bstride = new_stripe_stride ? new_stripe_stride : max_count * U.new_stride;
+            U.rec_bstride = recovery_stripe_stride ? recovery_stripe_stride : M * U.rec_stride;
+            if (stripes > 1 && ((d_old ? U.old_bstride : 0) | U.new_bstride | U.rec_bstride) % 4) force_bytes(g, S);
+            update_lists_dev(ctx, ws, high != 0, g, U, nsel, s);
+        });
+    });
 }
 
 rs_status rs_update_set_direct_max(rs_context *ctx, uint32_t k) {

@@ -455,6 +455,27 @@ struct UpdateArgs {
     ShardFormat fmt;
 };
 hipError_t launch_update(const UpdateArgs &A, hipStream_t stream);
+// The same with a list per stripe (k_update_lists, rs_update_device_batch_lists): stripe b
+// overwrites originals index[b * index_pitch + c], c < counts[b] (0: the stripe is left alone,
+// nothing of it read or written), and touches recovery row j only where sel[b * M + j] != 0
+// (sel = nullptr: every row).  logs is the table over every original, logs[j * N + i] =
+// log G[j][i] (launch_locate_log), zero coefficients as kUpdateNoCoef.  grid = (pack tiles,
+// groups of rows of M, stripes); stripes <= 65535.
+struct UpdateListsArgs {
+    const uint8_t *old_rows = nullptr, *new_rows = nullptr;  // a row per index, stripe b at b * bstride
+    uint8_t *rec = nullptr;
+    uint64_t old_stride = 0, new_stride = 0, rec_stride = 0;
+    uint64_t old_bstride = 0, new_bstride = 0, rec_bstride = 0;  // stripe b: + b * bstride
+    uint32_t packs = 0, index_pitch = 0, N = 0, M = 0, stripes = 1;
+    uint32_t rows_per_group = 1;
+    const uint32_t *counts = nullptr;  // stripes words
+    const uint32_t *index = nullptr;   // stripes x index_pitch words (index_pitch >= every count)
+    const uint8_t *sel = nullptr;      // stripes x M bytes, 4-byte aligned
+    const uint16_t *logs = nullptr;    // 4-byte aligned
+    const uint32_t *lut = nullptr;     // perm tables by log factor (rs_context::d_lut)
+    ShardFormat fmt;
+};
+hipError_t launch_update_lists(const UpdateListsArgs &A, hipStream_t stream);
 // Row-wise XOR over a row list (the re-encode route's two ends): for r < nrows,
 // out row (out_list ? list[r] : r) = a row (a_list ? list[r] : r) ^ b row (b_list
 // ? list[r] : r); b = nullptr: a copy of the a row.  list = nullptr: row r everywhere.

@@ -8,6 +8,8 @@
 //   k_coef_unit / k_coef_log   the coefficient step around that encode: the unit
 //                              stripe in, log G[j][c] out (once per index list)
 //   k_update                   the direct route: recovery_j ^= XOR_c delta_c * G[j][c]
+//   k_update_lists             the same with an index list and a row selection per stripe,
+//                              the logs read from the table over every original
 //   k_rows_xor                 out = a ^ b over a row list: the two ends of the
 //                              re-encode route (delta stripe in, recovery rows out)
 #include <cstdio>
@@ -106,6 +108,84 @@ __global__ __launch_bounds__(256) void k_update(const UpdateArgs A) {
     }
 }
 
+// k_update with one index list and one row selection per stripe (rs_update_device_batch_lists).
+// The logs come from the table over every original (pitch A.N), so the scalar chain is
+// index -> log -> perm table.  The indices are fetched beside the deltas: once per workgroup
+// for a count <= kUpdateTile, with every tile of every row above it (as k_update reloads its
+// deltas there).  blockIdx.y = group of rows_per_group recovery rows of A.M.
+template <bool OLD>
+__global__ __launch_bounds__(256) void k_update_lists(const UpdateListsArgs A) {
+    const uint64_t stripe = blockIdx.z;
+    const uint32_t count = const_words(A.counts)[stripe];
+    if (!count) return;  // an empty list, or a stripe the launch leaves out
+    const uint32_t pk = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = pk < A.packs;
+    const PackIO io = pack_io(A.fmt, ok ? pk : 0u);
+    const uint8_t *nw = A.new_rows + stripe * A.new_bstride + io.lo;
+    const uint8_t *od = OLD ? A.old_rows + stripe * A.old_bstride + io.lo : nullptr;
+    uint8_t *rec = A.rec + stripe * A.rec_bstride + io.lo;
+    const ConstWords logs = const_words(A.logs), lut = const_words(A.lut), sel = const_words(A.sel);
+    const ConstWords index = const_words(A.index + stripe * A.index_pitch);
+
+    uint32_t dl[kUpdateTile], dh[kUpdateTile], ix[kUpdateTile];
+    auto load_tile = [&](uint32_t c0) {
+        static_for<0, int(kUpdateTile)>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            const uint32_t c = c0 + uint32_t(i);
+            dl[i] = dh[i] = ix[i] = 0;
+            if (c < count) {
+                ix[i] = index[c];
+                if (ok) {
+                    const uint8_t *p = nw + uint64_t(c) * A.new_stride;
+                    dl[i] = ld_word(p, io);
+                    dh[i] = ld_word(p + io.hi_delta, io);
+                    if constexpr (OLD) {
+                        const uint8_t *q = od + uint64_t(c) * A.old_stride;
+                        dl[i] ^= ld_word(q, io);
+                        dh[i] ^= ld_word(q + io.hi_delta, io);
+                    }
+                }
+            }
+        });
+    };
+    const bool single = count <= kUpdateTile;  // the deltas and indices stay in registers across the rows
+    if (single) load_tile(0);
+
+    const uint32_t r0 = blockIdx.y * A.rows_per_group;
+    const uint32_t r1 = r0 + A.rows_per_group < A.M ? r0 + A.rows_per_group : A.M;
+    const uint32_t sel0 = uint32_t(stripe) * A.M;  // (at most 65535 stripes of at most 65536 rows)
+    for (uint32_t j = r0; j < r1; ++j) {
+        if (A.sel) {
+            const uint32_t e = sel0 + j;
+            if (!((sel[e >> 2] >> ((e & 3u) * 8u)) & 0xFFu)) continue;  // not selected: the row is never touched
+        }
+        uint32_t al = 0, ah = 0;
+        for (uint32_t c0 = 0; c0 < count; c0 += kUpdateTile) {
+            if (!single) load_tile(c0);
+            static_for<0, int(kUpdateTile)>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                const uint32_t c = c0 + uint32_t(i);
+                if (c < count) {
+                    const uint32_t e = j * A.N + ix[i];
+                    const uint32_t lg =
+                        __builtin_amdgcn_readfirstlane((logs[e >> 1] >> ((e & 1u) * 16u)) & 0xFFFFu);
+                    if (lg != kUpdateNoCoef) {  // a zero coefficient: nothing to add
+                        uint32_t t[kTableWords];
+#pragma unroll
+                        for (int w = 0; w < kTableWords; ++w) t[w] = lut[uint64_t(lg) * kTableWords + w];
+                        gf_muladd4(al, ah, dl[i], dh[i], t);
+                    }
+                }
+            });
+        }
+        if (ok) {
+            uint8_t *p = rec + uint64_t(j) * A.rec_stride;
+            st_word(p, ld_word(p, io) ^ al, io);
+            st_word(p + io.hi_delta, ld_word(p + io.hi_delta, io) ^ ah, io);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_rows_xor(const UpdateXorArgs A) {
     const uint32_t pk = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
     if (pk >= A.packs || r >= A.nrows) return;
@@ -157,6 +237,22 @@ hipError_t launch_update(const UpdateArgs &A0, hipStream_t s) {
     if (A.old_rows) k_update<true><<<grid, threads, 0, s>>>(A);
     else k_update<false><<<grid, threads, 0, s>>>(A);
     snprintf(launch_name_buf(), kLaunchNameBytes, "k_update<%s>", A.old_rows ? "true" : "false");
+    return hipGetLastError();
+}
+
+hipError_t launch_update_lists(const UpdateListsArgs &A0, hipStream_t s) {
+    if (!A0.packs || !A0.index_pitch || !A0.M || !A0.stripes) return hipSuccess;
+    if (A0.stripes > 65535 || A0.M > 65536) return hipErrorInvalidValue;
+    UpdateListsArgs A = A0;
+    const uint32_t threads = block_threads(A.packs), tiles = (A.packs + threads - 1) / threads;
+    // launch_update's rule, over every recovery row
+    const uint64_t units = uint64_t(A.M) * tiles * A.stripes;
+    A.rows_per_group = uint32_t(units / 1024 < 1 ? 1 : units / 1024 > 16 ? 16 : units / 1024);
+    const dim3 grid(tiles, (A.M + A.rows_per_group - 1) / A.rows_per_group, A.stripes);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    if (A.old_rows) k_update_lists<true><<<grid, threads, 0, s>>>(A);
+    else k_update_lists<false><<<grid, threads, 0, s>>>(A);
+    snprintf(launch_name_buf(), kLaunchNameBytes, "k_update_lists<%s>", A.old_rows ? "true" : "false");
     return hipGetLastError();
 }
 

@@ -115,6 +115,8 @@ _sig("rs_update_device", _int, _vp, _int, _u64, _u64, _u64, ctypes.POINTER(_u64)
      ctypes.c_char_p, _vp, _E)
 _sig("rs_update_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, ctypes.POINTER(_u64), _u64, _vp, _u64, _u64, _vp,
      _u64, _u64, _vp, _u64, _u64, ctypes.c_char_p, _vp, _E)
+_sig("rs_update_device_batch_lists", _int, _vp, _int, _u64, _u64, _u64, _u64, ctypes.POINTER(_u64),
+     ctypes.POINTER(ctypes.c_uint32), _u64, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _E)
 _sig("rs_update_set_direct_max", _int, _vp, ctypes.c_uint32)
 _sig("rs_verify_device", _int, _vp, _int, _u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_char_p, _vp, _vp, _E)
 _sig("rs_verify_device_batch", _int, _vp, _int, _u64, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _u64,
@@ -1109,6 +1111,43 @@ def update_device_batch(original_count: int, recovery_count: int, shard_bytes: i
                                        None if d_old is None else d_old.data_ptr(), o_row, o_b, d_new.data_ptr(),
                                        n_row, n_b, d_recovery.data_ptr(), r_row, r_b, rows, _stream(stream),
                                        ctypes.byref(err)), err)
+
+
+def update_device_batch_lists(original_count: int, recovery_count: int, shard_bytes: int, indices, d_old, d_new,
+                              d_recovery, recovery_rows=None, stream=None, rate_: int = RATE_DEFAULT,
+                              ctx: Optional[Context] = None) -> None:
+    """update_device on a batch of stripes, each with its OWN index list and its OWN row mask
+    (rs_update_device_batch_lists).  indices: one sequence of original indices per stripe (an
+    empty one leaves the stripe alone); max_count is the longest of them.  d_old / d_new
+    [stripes, max_count, shard_bytes]: row c of stripe b is the old / new content of original
+    indices[b][c], rows past len(indices[b]) are never read; d_old=None: d_new holds the deltas.
+    d_recovery [stripes, recovery_count, shard_bytes].  recovery_rows: None (every row) or a
+    [stripes, recovery_count] array of 0/1."""
+    ctx = ctx or default_context()
+    _validate(rate_, original_count, recovery_count, shard_bytes)
+    lists = [[int(i) for i in stripe] for stripe in indices]
+    if any(i < 0 for stripe in lists for i in stripe):
+        raise ValueError("indices: an original index cannot be negative")
+    n, k = len(lists), max((len(stripe) for stripe in lists), default=0)
+    flat = (_u64 * max(1, n * k))()
+    for b, stripe in enumerate(lists):
+        flat[b * k:b * k + len(stripe)] = stripe
+    counts = (ctypes.c_uint32 * max(1, n))(*[len(stripe) for stripe in lists])
+    rows = None if recovery_rows is None else _stripe_masks(recovery_rows, n, recovery_count, "recovery_rows")
+    if d_old is not None:
+        _check_matrix(d_old, k, shard_bytes, "d_old", 3)
+    _check_matrix(d_new, k, shard_bytes, "d_new", 3)
+    _check_matrix(d_recovery, recovery_count, shard_bytes, "d_recovery", 3)
+    if d_new.shape[0] != n or d_recovery.shape[0] != n or (d_old is not None and d_old.shape[0] != n):
+        raise ValueError(f"batches differ in stripe count from the {n} index lists")
+    (o_row, o_b) = (0, 0) if d_old is None else _batch_strides(d_old)
+    (n_row, n_b), (r_row, r_b) = _batch_strides(d_new), _batch_strides(d_recovery)
+    err = _RsError()
+    _raise(_lib.rs_update_device_batch_lists(ctx.handle, rate_, original_count, recovery_count, shard_bytes, n, flat,
+                                             counts, k, None if d_old is None else d_old.data_ptr(), o_row, o_b,
+                                             d_new.data_ptr(), n_row, n_b, d_recovery.data_ptr(), r_row, r_b,
+                                             None if rows is None else rows.ctypes.data, _stream(stream),
+                                             ctypes.byref(err)), err)
 
 
 def update_set_direct_max(k: int, ctx: Optional[Context] = None) -> None:
